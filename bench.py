@@ -1,6 +1,17 @@
 """Headline benchmark: SVGD inner step, N=65536 particles, d=8, GMM(k=4), fp64.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: set up, W warm-up
+steps and SETTLE_STEPS more untimed ones (so that its figure is the steady
+state the median run of --full reports: the first steps' median brackets are
+sampled, the later ones predicted from the medians before them), one timed
+run of exactly K steps, the result line.  --dump-outputs DIR
+writes what the last timed step computed (DIR/particles.npy: X after it,
+DIR/scale.npy: its scale a and median; float64); the inputs are the same
+from run to run.  Everything else described below (the repeated timed runs,
+the diagnostic pass and its roofline / phases / diag records, the amdsmi
+records, the CPU baseline and its accuracy record) is measured with --full.
 
 BASELINE.json metric: particle-updates/s (N x steps / s) at N=65536, d=8
 (cfg3).  One step = SVGD::Step of the reference (SVGD.hpp:373-400):
@@ -10,13 +21,13 @@ inside the timed region, X resident in HBM.  For N GPUs (one process each,
 torchrun) the particles are sharded by rows and the context all-gathers X and
 G over RCCL every step; N is fixed (strong scaling, as the metric specifies).
 
-Protocol: W warm-up steps, then `--repeats` (5) timed runs of
-exactly K steps, each bracketed by barrier + device sync; value/ms_per_step
-are the median run (per run the slowest rank).  Then one untimed diagnostic
-pass of K steps with extra HIP events (the phi kernel alone, the device's
-wait for G, collectives).
+Protocol: W warm-up steps, then one timed run of exactly K
+steps (--full: `--repeats` (5) such runs), each bracketed by barrier + device
+sync; value/ms_per_step are the median run (per run the slowest rank).  With
+--full, then one untimed diagnostic pass of K steps with extra HIP events (the
+phi kernel alone, the device's wait for G, collectives).
 
-The JSON line also carries
+With --full the JSON line also carries
   roofline     -- the phi kernel (dominant): algorithmic flop per launch
                   (rows x N x (5d+4)) / its average launch time
                   from HIP events around that launch alone (diagnostic pass),
@@ -354,6 +365,120 @@ def _kernel_src_sha():
     return h.hexdigest()[:16]
 
 
+def roofline(kname, phi_kernel_ms, flops_launch, n, d, dtype, wkey, clk):
+    """--full: the roofline record of the phi kernel `kname` -- one launch of
+    phi_kernel_ms (diagnostic pass; None without one) and flops_launch
+    algorithmic flops, at the workload (n, d, wkey ranks: the key of the
+    committed profiles); clk: the gfx clock amdsmi read during that pass."""
+    achieved = flops_launch / (phi_kernel_ms / 1e3) / 1e12 if phi_kernel_ms else None
+    peak = FP32_PEAK_TFLOPS if dtype == "f32" else FP64_PEAK_TFLOPS
+    b3 = None
+    if kname.startswith("k_phi_b3"):
+        # fp32 products as six bf16 part products on the bf16 matrix cores:
+        # the MFMA work per ordered pair is 6 x 2 x (KP + 16 NCB) flops
+        # (Gram over KP padded dims, P.V over the padded V width), so the
+        # ceiling for the algorithmic flops is the bf16 dense peak scaled
+        # by algorithmic / MFMA flops
+        kp = 32 if d <= 32 else 64
+        ncb = d // 16 if d % 16 == 0 else (d + 16) // 16
+        mfma_pair = 6.0 * 2.0 * (kp + 16 * ncb)
+        peak = BF16_PEAK_TFLOPS * (5 * d + 4) / mfma_pair
+        b3 = {"peak_basis": f"bf16 dense MFMA peak {BF16_PEAK_TFLOPS:.0f} TF/s x algorithmic / MFMA flops "
+                            f"per pair ({5 * d + 4} / {mfma_pair:.0f}: six bf16 part products per fp32 product)",
+              "fp32_mfma_peak_frac": (achieved / FP32_PEAK_TFLOPS) if achieved else None,
+              "bf16_mfma_tflops": (achieved * mfma_pair / (5 * d + 4)) if achieved else None}
+    # committed PMC passes (not this run) count only for the same kernel
+    # (name + template arguments, svgd_phi_kernel_name), the same kernel
+    # source (hash of svgd_kernels.hip) and the same workload (N, d, P)
+    src_sha = _kernel_src_sha()
+
+    def committed(name):
+        path = os.path.join(ROOT, "profiles", name)
+        if not os.path.exists(path):
+            return None
+        with open(path) as f:
+            recs = json.load(f)
+        for p in recs if isinstance(recs, list) else [recs]:  # one record per kernel / workload
+            if (p.get("n") == n and p.get("d") == d and p.get("world") == wkey and kname in p.get("kernel", "")
+                    and p.get("src_sha16") == src_sha):
+                return p
+        return None
+
+    pmc = committed("phi_pmc_traffic.json")
+    traffic = pmc.get("bytes_per_launch") if pmc else None
+    issue = committed("phi_pmc_issue.json")
+    row_kernel = dtype == "f64" and d <= 16
+    out = {
+        # fp64 d <= 16: VALU row stream (f64 MFMA shares the VALU issue
+        # slots on gfx950, DESIGN §4); otherwise the MFMA tile kernel.
+        # avg_launch_ms: HIP events around the phi kernel launch alone
+        # (diagnostic pass after the timed runs; k_phi_rows without
+        # its reduce), so it is comparable with rocprof's kernel mean
+        "kernel": ("k_phi_sym (fused RBF + grad + phi contraction, symmetric: one Gram and one exp "
+                   "per unordered pair feed both particles; fp64 VALU)"
+                   if kname.startswith("k_phi_sym") else
+                   "k_phi_rows (fused RBF + grad + phi contraction, fp64 VALU row stream)"
+                   if row_kernel else
+                   "k_phi_b3 (fused RBF + grad + phi contraction, fp32-accurate on the bf16 "
+                   "matrix cores: three-part operands, six part products)"
+                   if b3 else
+                   "k_phi_f32s (fused RBF + grad + phi contraction, streamed fp32 MFMA tiles)"
+                   if dtype == "f32" and d > 12 else
+                   "k_phi (fused RBF + grad + phi contraction, MFMA tiles)"),
+        "timed_span": "the phi kernel launch alone (HIP events, diagnostic pass)",
+        "bound": "valu" if row_kernel else "mfma",
+        "achieved": achieved,
+        "peak": peak,
+        "unit": "TFLOP/s",
+        "frac": (achieved / peak) if achieved else None,
+        "traffic": traffic,
+        "traffic_source": (pmc or {}).get("source") if traffic else
+                          f"none committed for {kname} at this source hash / workload",
+        "kernel_launched": kname,
+        "avg_launch_ms": phi_kernel_ms,
+        "flop_per_launch": flops_launch,
+    }
+    if b3:
+        out.update(b3)
+    if achieved and clk:
+        # the flop fraction against the peak at the clock this run held
+        # under the phi kernel (amdsmi, same run): the ceiling this
+        # instruction mix can reach on this box
+        out["clock_mhz_under_load"] = clk
+        out["frac_at_load_clock"] = achieved / (peak * clk / 2400.0)
+    if issue is not None:
+        out.update({"valu_issue_util": issue["valu_issue_util"], "issue_source": issue["source"]})
+    return out
+
+
+DUMP_MAX_BYTES = 64 * 1000 * 1000  # --dump-outputs: all files together
+SETTLE_STEPS = 16  # a plain run: untimed steps between the warm-up and the timed run
+
+
+def dump_outputs(out_dir, X, a, med):
+    """--dump-outputs: the last timed step's results as float64 .npy files --
+    particles.npy (X after the step, (n, d)) and scale.npy ([a, median]).
+    An X above DUMP_MAX_BYTES is written as a fixed seeded row sample, the
+    rows' indices in particle_rows.npy.  out_dir=None (a rank other than 0)
+    writes nothing."""
+    if out_dir is None:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    n, d = X.shape
+    budget = DUMP_MAX_BYTES - 4096  # the .npy headers and scale.npy
+    rows_file = os.path.join(out_dir, "particle_rows.npy")
+    if os.path.exists(rows_file):
+        os.remove(rows_file)  # an earlier dump's
+    if X.nbytes > budget:
+        keep = budget // ((d + 1) * 8)  # a row and its index
+        rows = np.sort(np.random.default_rng(0x5EED).choice(n, size=keep, replace=False))
+        np.save(rows_file, rows.astype(np.float64))
+        X = X[rows]
+    np.save(os.path.join(out_dir, "particles.npy"), X)
+    np.save(os.path.join(out_dir, "scale.npy"), np.array([a, med], dtype=np.float64))
+
+
 def spawn_ranks(nproc, argv=None, poll=0.05, grace=20.0):
     """`bench.py --gpus N` without a launcher: start N rank processes (one per
     GPU) before anything touches a GPU and poll them.  The first rank that
@@ -410,18 +535,30 @@ def main():
     ap.add_argument("--k", type=int, default=4)
     ap.add_argument("--cpu-rows", type=int, default=None, help="cpu_baseline row sample (default: the config's)")
     ap.add_argument("--cpu-rows-1t", type=int, default=2048)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--repeats", type=int, default=5, help="timed runs of K steps; the median is reported")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline and accuracy record")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: --repeats timed runs, the diagnostic pass "
+                         "(roofline, phases, diag), the amdsmi records, the CPU baseline and accuracy record")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed: DIR/particles.npy (X), "
+                         "DIR/scale.npy (scale a, median); float64")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="--full: timed runs of K steps, the median is reported (default 5; a plain run times one)")
     ap.add_argument("--sim-world", type=int, default=0,
                     help="measurement only: time rank 0's share of a P-rank step on one GPU "
                          "(no collectives; results are not the step's) -- not a headline line")
-    ap.add_argument("--no-diag", action="store_true", help="skip the untimed diagnostic pass")
+    ap.add_argument("--no-diag", action="store_true", help="--full: skip the untimed diagnostic pass")
     ap.add_argument("--dtype", choices=["f64", "f32"], default=None,
                     help="compute dtype of the O(N^2) work (default: the config's; cfg5 is f32)")
     ap.add_argument("--device-model", action="store_true",
                     help="grad log p on the device (SURVEY 8(f) rank 1) instead of the host; "
                          "not the north-star configuration")
     args = ap.parse_args()
+    if args.repeats is not None and not args.full:
+        ap.error("--repeats needs --full (a plain run times exactly --steps steps)")
+    if args.dump_outputs and args.sim_world > 1:
+        ap.error("--dump-outputs: a --sim-world context has no results (its step is one rank's share)")
+    repeats = (5 if args.repeats is None else args.repeats) if args.full else 1
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
 
@@ -483,13 +620,22 @@ def main():
     # event between two kernels costs a ~6 us dispatch gap); the phase split
     # comes from the diagnostic pass below
     ctx.check(ctx.lib.svgd_set_timing(ctx.h, 0))
+    if not args.full:
+        # the one timed run of a plain run starts where the median run of
+        # --full lies: past the first steps on the event-free path, whose
+        # median brackets are sampled (the tracked bracket is predicted from
+        # the medians of the steps before)
+        for _ in range(SETTLE_STEPS):
+            step()
+        ctx.sync()
+        ctx.diagnostics()  # (reset)
 
-    # the median of `repeats` timed runs of exactly K steps, each
-    # bracketed by barrier + device sync; the GPU's clock/power sampled by
-    # amdsmi over the same span
-    mon = GpuMonitor(local_rank).start()
+    # the median of `repeats` timed runs of exactly K steps (a
+    # plain run: one), each bracketed by barrier + device sync; --full: the
+    # GPU's clock/power sampled by amdsmi over the same span
+    mon = GpuMonitor(local_rank).start() if args.full else None
     runs = []
-    for _ in range(args.repeats):
+    for _ in range(repeats):
         barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -499,15 +645,20 @@ def main():
         torch.cuda.synchronize()
         barrier()
         runs.append(time.perf_counter() - t0)
-    gpu_timed = mon.stop()
+    gpu_timed = mon.stop() if mon is not None else None
     phi_ms, med_ms, cnt = ctypes.c_double(), ctypes.c_double(), ctypes.c_int64()
     host_timed = ctx.diagnostics()  # host-side clocks of the timed steps (always on)
+    if args.dump_outputs:
+        # what a caller of the timed path holds after its last step
+        # (svgd_get_particles is a collective: every rank calls it)
+        a_t, med_t, _ = ctx.last_scale()
+        dump_outputs(args.dump_outputs if rank == 0 else None, ctx.get_particles(), a_t, med_t)
 
     # diagnostic pass (untimed): the phi kernel alone, the device's wait for
     # G before the phi chain, collectives -- extra events, so not in the runs
     diag = None
     gpu_diag = None
-    if not args.no_diag:
+    if args.full and not args.no_diag:
         ctx.check(ctx.lib.svgd_set_timing(ctx.h, 2))
         mon.start()
         for _ in range(args.steps):
@@ -532,15 +683,6 @@ def main():
 
     mine = {
         "rank": rank, "rows": rows,
-        # phase events at phase boundaries, from the diagnostic pass (level 2:
-        # its extra events make these spans a few us longer than the timed
-        # steps'):
-        # "phi" runs from the median's end (so it holds any wait for G) to the
-        # update's end, "median" from the previous step's end (so it holds the
-        # gap between steps) to the scale; the diagnostic pass separates both
-        "phases_ms_per_step": {"phi_incl_wait_for_g": per_step(phi_ms.value, args.steps if diag is not None else 0),
-                               "median_incl_step_gap": per_step(med_ms.value, args.steps if diag is not None else 0),
-                               "source": "diagnostic pass"},
         "host_ms_per_step": {"grad": per_step(host_timed["host_grad_ms"], host_timed["steps"]),
                              "xwait": per_step(host_timed["host_xwait_ms"], host_timed["steps"]),
                              "job": per_step(host_timed["host_job_ms"], host_timed["steps"]),
@@ -560,6 +702,17 @@ def main():
                              "mean_band_share": (host_timed["trk_band"] / host_timed["trk_steps"]
                                                  if host_timed.get("trk_steps") else None)},
     }
+    if args.full:
+        # phase events at phase boundaries, from the diagnostic pass (level 2:
+        # its extra events make these spans a few us longer than the timed
+        # steps'):
+        # "phi" runs from the median's end (so it holds any wait for G) to the
+        # update's end, "median" from the previous step's end (so it holds the
+        # gap between steps) to the scale; the diagnostic pass separates both
+        mine["phases_ms_per_step"] = {
+            "phi_incl_wait_for_g": per_step(phi_ms.value, args.steps if diag is not None else 0),
+            "median_incl_step_gap": per_step(med_ms.value, args.steps if diag is not None else 0),
+            "source": "diagnostic pass"}
     # phi launches per step: 2 when the context runs phi in row halves
     # (P > 1 with few gradient threads per rank)
     parts = max(1, round(diag["phi_kernel_n"] / args.steps)) if diag is not None and diag["phi_kernel_n"] else 1
@@ -580,49 +733,6 @@ def main():
         dist.all_gather_object(per_rank, mine)
 
     if rank == 0:
-        phi_step_ms = (mine.get("diag_ms_per_step") or {}).get("phi_kernel")
-        phi_kernel_ms = phi_step_ms / parts if phi_step_ms else None  # one launch
-        flops_launch = float(rows) * n * (5 * d + 4) / parts
-        achieved = flops_launch / (phi_kernel_ms / 1e3) / 1e12 if phi_kernel_ms else None
-        peak = FP32_PEAK_TFLOPS if dtype == "f32" else FP64_PEAK_TFLOPS
-        b3 = None
-        if ctx.phi_kernel_name().startswith("k_phi_b3"):
-            # fp32 products as six bf16 part products on the bf16 matrix cores:
-            # the MFMA work per ordered pair is 6 x 2 x (KP + 16 NCB) flops
-            # (Gram over KP padded dims, P.V over the padded V width), so the
-            # ceiling for the algorithmic flops is the bf16 dense peak scaled
-            # by algorithmic / MFMA flops
-            kp = 32 if d <= 32 else 64
-            ncb = d // 16 if d % 16 == 0 else (d + 16) // 16
-            mfma_pair = 6.0 * 2.0 * (kp + 16 * ncb)
-            peak = BF16_PEAK_TFLOPS * (5 * d + 4) / mfma_pair
-            b3 = {"peak_basis": f"bf16 dense MFMA peak {BF16_PEAK_TFLOPS:.0f} TF/s x algorithmic / MFMA flops "
-                                f"per pair ({5 * d + 4} / {mfma_pair:.0f}: six bf16 part products per fp32 product)",
-                  "fp32_mfma_peak_frac": (achieved / FP32_PEAK_TFLOPS) if achieved else None,
-                  "bf16_mfma_tflops": (achieved * mfma_pair / (5 * d + 4)) if achieved else None}
-        # committed PMC passes (not this run) count only for the same kernel
-        # (name + template arguments, svgd_phi_kernel_name), the same kernel
-        # source (hash of svgd_kernels.hip) and the same workload (N, d, P)
-        wkey = args.sim_world if args.sim_world > 1 else world  # the profiles' world
-        kname = ctx.phi_kernel_name()
-        src_sha = _kernel_src_sha()
-
-        def committed(name):
-            path = os.path.join(ROOT, "profiles", name)
-            if not os.path.exists(path):
-                return None
-            with open(path) as f:
-                recs = json.load(f)
-            for p in recs if isinstance(recs, list) else [recs]:  # one record per kernel / workload
-                if (p.get("n") == n and p.get("d") == d and p.get("world") == wkey and kname in p.get("kernel", "")
-                        and p.get("src_sha16") == src_sha):
-                    return p
-            return None
-
-        pmc = committed("phi_pmc_traffic.json")
-        traffic = pmc.get("bytes_per_launch") if pmc else None
-        issue = committed("phi_pmc_issue.json")
-        row_kernel = dtype == "f64" and d <= 16
         out = {
             "metric": METRIC,
             "value": n * args.steps / elapsed,
@@ -630,6 +740,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "settle_steps": 0 if args.full else SETTLE_STEPS,
             "ms_per_step": elapsed / args.steps * 1e3,
             "higher_is_better": True,
             "scaling": "strong",
@@ -644,61 +755,27 @@ def main():
             },
             "repeats": {"n": len(runs), "rule": "value/ms_per_step = median run (max over ranks per run)",
                         "ms_per_step": [r / args.steps * 1e3 for r in runs]},
-            "roofline": {
-                # fp64 d <= 16: VALU row stream (f64 MFMA shares the VALU issue
-                # slots on gfx950); otherwise the MFMA tile kernel.
-                # avg_launch_ms: HIP events around the phi kernel launch alone
-                # (diagnostic pass after the timed runs; k_phi_rows without
-                # its reduce), so it is comparable with rocprof's kernel mean
-                "kernel": ("k_phi_sym (fused RBF + grad + phi contraction, symmetric: one Gram and one exp "
-                           "per unordered pair feed both particles; fp64 VALU)"
-                           if kname.startswith("k_phi_sym") else
-                           "k_phi_rows (fused RBF + grad + phi contraction, fp64 VALU row stream)"
-                           if row_kernel else
-                           "k_phi_b3 (fused RBF + grad + phi contraction, fp32-accurate on the bf16 "
-                           "matrix cores: three-part operands, six part products)"
-                           if b3 else
-                           "k_phi_f32s (fused RBF + grad + phi contraction, streamed fp32 MFMA tiles)"
-                           if dtype == "f32" and d > 12 else
-                           "k_phi (fused RBF + grad + phi contraction, MFMA tiles)"),
-                "timed_span": "the phi kernel launch alone (HIP events, diagnostic pass)",
-                "bound": "valu" if row_kernel else "mfma",
-                "achieved": achieved,
-                "peak": peak,
-                "unit": "TFLOP/s",
-                "frac": (achieved / peak) if achieved else None,
-                "traffic": traffic,
-                "traffic_source": (pmc or {}).get("source") if traffic else
-                                  f"none committed for {kname} at this source hash / workload",
-                "kernel_launched": kname,
-                "avg_launch_ms": phi_kernel_ms,
-                "flop_per_launch": flops_launch,
-            },
-            "phases_ms_per_step": mine["phases_ms_per_step"],
             "host_ms_per_step": mine["host_ms_per_step"],
             "tracked_brackets": mine["tracked_brackets"],
-            "diag_ms_per_step": mine.get("diag_ms_per_step"),
-            "gpu_timed": gpu_timed,
-            "gpu_diag": gpu_diag,
             "median_path": ["direct", "bracket", "fallback", "rebracket"][path],
             "scale_a": a,
             # every SVGD_* variable of this run (library knobs; none by default)
             "env_knobs": {k: v for k, v in sorted(os.environ.items()) if k.startswith("SVGD_")},
         }
-        if b3:
-            out["roofline"].update(b3)
+        if args.full:
+            phi_step_ms = (mine.get("diag_ms_per_step") or {}).get("phi_kernel")
+            out.update({
+                "roofline": roofline(ctx.phi_kernel_name(), phi_step_ms / parts if phi_step_ms else None,
+                                     float(rows) * n * (5 * d + 4) / parts, n, d, dtype,
+                                     args.sim_world if args.sim_world > 1 else world,
+                                     (gpu_diag or {}).get("gfxclk_mhz_median")),
+                "phases_ms_per_step": mine["phases_ms_per_step"],
+                "diag_ms_per_step": mine.get("diag_ms_per_step"),
+                "gpu_timed": gpu_timed,
+                "gpu_diag": gpu_diag,
+            })
         if world > 1:
             out["per_rank"] = per_rank
-        clk = (gpu_diag or {}).get("gfxclk_mhz_median")
-        if achieved and clk:
-            # the flop fraction against the peak at the clock this run held
-            # under the phi kernel (amdsmi, same run): the ceiling this
-            # instruction mix can reach on this box
-            out["roofline"]["clock_mhz_under_load"] = clk
-            out["roofline"]["frac_at_load_clock"] = achieved / (peak * clk / 2400.0)
-        if issue is not None:
-            out["roofline"].update({"valu_issue_util": issue["valu_issue_util"],
-                                    "issue_source": issue["source"]})
         if args.sim_world > 1:
             out["metric"] = (f"per-rank step time of a {args.sim_world}-GPU run, simulated on one GPU "
                              f"(rank 0's rows and pair share, no collectives; not the headline)")
@@ -710,7 +787,7 @@ def main():
                 desc = desc.replace("fp32 compute", "fp64 compute") + (", fp32 compute" if dtype == "f32" and "fp32" not in desc else "")
             out["metric"] = (f"particle-updates/s, {desc}"
                              f"{', device grad log p' if args.device_model else ''} (not the headline config)")
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             # the device's phi_hat of X0 for the CPU leg's accuracy record,
             # after the timed runs (X0 set again: the centring, median and phi
             # of X0 are those of a fresh context).  Run before the warm-up it

@@ -5,6 +5,7 @@
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out/ab
 source tools/fault_guard.sh
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # median of the repeated runs, phases and diag records
 for round in $(seq ${ROUNDS:-2}); do
   for spec in "$@"; do
     name=${spec%%:*}; envs=${spec#*:}

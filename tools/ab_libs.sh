@@ -6,6 +6,7 @@
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out/ab
 source tools/fault_guard.sh
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # median of the repeated runs, phases record
 LIB=svgdcpp_amd/libsvgdcpp_amd.so
 cp $LIB /tmp/ab_cur.so
 for round in $(seq ${ROUNDS:-2}); do

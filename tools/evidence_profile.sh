@@ -43,7 +43,7 @@ if has sim8tl; then
     envs=""; [ $form = rows ] && envs="SVGD_PHI_SYM=0"
     (cd /tmp && export TMPDIR=/tmp && for kv in $envs; do export "$kv"; done && \
      timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $REPO/$O/sim8_$form -o run --output-format csv \
-       -- python3 $REPO/bench.py --sim-world 8 --steps 20 --warmup 3 --no-cpu > $REPO/$O/sim8_${form}_prof.log 2>&1) || exit 1
+       -- python3 $REPO/bench.py --full --sim-world 8 --steps 20 --warmup 3 --no-cpu > $REPO/$O/sim8_${form}_prof.log 2>&1) || exit 1
     fault_guard $O/sim8_${form}_prof.log
     python3 tools/step_timeline.py $O/sim8_$form/run_kernel_trace.csv > $O/step_timeline_sim8_$form.txt
     tail -1 $O/step_timeline_sim8_$form.txt
@@ -57,7 +57,7 @@ fi
 if has sim; then
   b() { # name timeout args...
     local name=$1 t=$2; shift 2
-    timeout -k 10 $t python bench.py "$@" > $O/$name.log 2>&1 || { echo "FAIL $name"; tail -5 $O/$name.log; exit 1; }
+    timeout -k 10 $t python bench.py --full "$@" > $O/$name.log 2>&1 || { echo "FAIL $name"; tail -5 $O/$name.log; exit 1; }
     fault_guard $O/$name.log
     tail -1 $O/$name.log > $O/$name.json
     python3 -c "import json,sys; d=json.load(open('$O/$name.json')); dg=d.get('diag_ms_per_step') or {}; h=d['host_ms_per_step']; print('$name', round(d['ms_per_step'],4), 'phi', dg.get('phi_kernel'), 'parts', dg.get('phi_launches_per_step'), 'wait', dg.get('phi_wait_for_g'), 'thr', h.get('threads'), 'trk', d['tracked_brackets'], d.get('phi_kernel'))"

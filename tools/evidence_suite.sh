@@ -17,7 +17,7 @@ if [ -z "$SKIP_PYTEST" ]; then
 fi
 b() { # name timeout args...
   local name=$1 t=$2; shift 2
-  timeout -k 10 $t python bench.py "$@" > $O/$name.log 2>&1 || { echo "FAIL $name"; tail -5 $O/$name.log; exit 1; }
+  timeout -k 10 $t python bench.py --full "$@" > $O/$name.log 2>&1 || { echo "FAIL $name"; tail -5 $O/$name.log; exit 1; }
   fault_guard $O/$name.log
   tail -1 $O/$name.log > $O/$name.json
   python3 -c "import json,sys; d=json.load(open('$O/$name.json')); r=d['roofline']; cb=d.get('cpu_baseline') or {}; print('$name', round(d['ms_per_step'],4), d['value'], r.get('kernel_launched'), 'frac', r.get('frac'), 'traffic', r.get('traffic'), 'cpu', cb.get('value'), 'runs', [round(x,3) for x in d['repeats']['ms_per_step']])"

@@ -9,6 +9,7 @@
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 source tools/fault_guard.sh
+REPO=$(pwd)
 OUT=gpurun_out/${TAG:-ab}
 mkdir -p $OUT
 if [ -n "${TESTS:-}" ]; then
@@ -23,8 +24,8 @@ restore() { cp /tmp/gpu_ab_cur.so svgdcpp_amd/libsvgdcpp_amd.so; }
 if [ -n "${KERNELS:-}" ]; then
   for v in $VARIANTS; do
     cp tools/ablibs/$v.so svgdcpp_amd/libsvgdcpp_amd.so
-    ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 200 rocprofv3 --kernel-trace --stats -d "$GRAFT_REPO_ROOT/$OUT/prof_$v" -o run \
-        --output-format csv -- python3 "$GRAFT_REPO_ROOT/bench.py" --steps 20 --warmup 2 --no-cpu > "$GRAFT_REPO_ROOT/$OUT/prof_$v.log" 2>&1 ) \
+    ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 200 rocprofv3 --kernel-trace --stats -d "$REPO/$OUT/prof_$v" -o run \
+        --output-format csv -- python3 "$REPO/bench.py" --full --steps 20 --warmup 2 --no-cpu > "$REPO/$OUT/prof_$v.log" 2>&1 ) \
       || { echo "$v rocprof failed"; restore; exit 1; }
     fault_guard $OUT/prof_$v.log
     python3 - "$OUT/prof_$v" "$v" "$KERNELS" <<'PY'

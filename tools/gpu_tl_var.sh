@@ -7,6 +7,7 @@ REPO=$(pwd)
 OUT=$REPO/gpurun_out/tlvar
 mkdir -p $OUT
 source tools/fault_guard.sh
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # the repeated timed runs: step_timeline.py reads their middle step
 for v in $VARIANTS; do
   name=${v%%:*}; envs=${v#*:}
   (cd /tmp && export TMPDIR=/tmp && for kv in ${envs//,/ }; do [ "$kv" = "-" ] || export "$kv"; done && \

@@ -5,6 +5,7 @@ OUT="$REPO/gpurun_out/pmc${TAG:-}"
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 i=0
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # the repeated timed runs and the diagnostic pass
 for set in "${@}"; do
   i=$((i+1))
   timeout -k 10 300 rocprofv3 --kernel-trace --pmc $set -d "$OUT/p$i" -o run --output-format csv \

@@ -7,6 +7,7 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 60 rocprofv3 --list-avail > "$OUT/avail.txt" 2>&1 || true
 i=0
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # the repeated timed runs (and the diagnostic pass unless --no-diag)
 for set in "$@"; do
   i=$((i+1))
   timeout -s KILL 120 rocprofv3 --kernel-trace --pmc $set -d "$OUT/p$i" -o run --output-format csv \

@@ -11,6 +11,7 @@
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 N=${1:-2}
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # --repeats and every rank's diag record
 OUT=${2:-gpurun_out/bench_mr$N.json}
 SVGD_BENCH_DEVICE=0 SVGD_HOSTCOMM=svgd_bench_$$ SVGD_DEBUG_COLL=1 OMP_NUM_THREADS=4 timeout -k 10 400 \
   python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 \

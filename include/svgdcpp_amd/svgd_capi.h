@@ -296,6 +296,23 @@ int svgd_set_device_model(svgd_ctx *ctx, const void *model);
  * (shard layout like svgd_get_shard). */
 int svgd_device_logp_grad(svgd_ctx *ctx, double *G_shard_out);
 
+/* Kernelized Stein discrepancy of the current particles with the isotropic
+ * RBF kernel k = exp(-a |x - y|^2), whatever scale method the context steps
+ * with.  For s_i = grad log p(x_i), r = x_i - x_j:
+ *   u_ij   = k_ij [ s_i.s_j + 2a (s_i - s_j).r + 2ad - 4a^2 |r|^2 ]
+ *   row_i  = (1/N) sum_j u_ij
+ *   KSD2_V = (1/N) sum_i row_i                     (V-statistic, >= 0)
+ *   KSD2_U = (1/(N(N-1))) sum_{i != j} u_ij        (U-statistic; NaN for N < 2)
+ * G_shard: this rank's rows of grad log p at the current particles, as for
+ * svgd_phi; NULL evaluates the device model (svgd_set_device_model).  Any
+ * output may be NULL; rows_shard_out takes this rank's row_i.  fp64 for
+ * SVGD_F32 contexts too; two calls on the same state return the same bits.
+ * A pure observer: particles, optimizer state, the last scale and the
+ * median's history are left as they were.  Collective in multi-GPU mode
+ * (every rank gets the same two scalars). */
+int svgd_ksd(svgd_ctx *ctx, const double *G_shard, double a, double *ksd2_v, double *ksd2_u,
+             double *rows_shard_out);
+
 /* ---- host-only planning helpers (no GPU needed) ------------------------ */
 
 /* Row shard of rank r among `world` for n particles: equal chunks of

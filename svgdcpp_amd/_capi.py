@@ -85,6 +85,7 @@ SIGNATURES = {
     "svgd_get_scale_matrix": (ctypes.c_int, [_P, _D]),
     "svgd_set_device_model": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "svgd_device_logp_grad": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]),
+    "svgd_ksd": (ctypes.c_int, [_P, _D, ctypes.c_double, _D, _D, _D]),
     "svgd_plan_rows": (None, [_I64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
     "svgd_plan_median_ranks": (ctypes.c_int, [_I64, ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
     "svgd_plan_pair_tiles": (_I64, [_I64, ctypes.c_int, ctypes.c_int, ctypes.c_int]),

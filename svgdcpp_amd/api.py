@@ -821,6 +821,22 @@ class Context:
     def step_device(self):
         self.check(self.lib.svgd_step(self.h, None))
 
+    def ksd(self, G_shard=None, a=None, rows=False):
+        """Kernelized Stein discrepancy of the current particles (svgd_ksd):
+        (KSD²_V, KSD²_U), with this rank's row_i = (1/N) Σ_j u_ij appended
+        when rows=True.  G_shard: this rank's rows of ∇log p (None: the device
+        model); a: the RBF scale (None: median_scale() of the particles)."""
+        if a is None:
+            a = self.median_scale()[0]
+        G = None if G_shard is None else np.ascontiguousarray(G_shard, dtype=np.float64)
+        if G is not None and G.shape != (self.row1 - self.row0, self.dim):
+            raise DimensionMismatchException("Log-gradient shard has incorrect dimensions.")
+        v, u = ctypes.c_double(), ctypes.c_double()
+        out = np.empty(self.row1 - self.row0) if rows else None
+        self.check(self.lib.svgd_ksd(self.h, C.dptr(G), float(a), ctypes.byref(v), ctypes.byref(u),
+                                     C.dptr(out)))
+        return (v.value, u.value, out) if rows else (v.value, u.value)
+
     def sync(self):
         self.check(self.lib.svgd_sync(self.h))
 
@@ -899,6 +915,7 @@ class SVGD:
         self.log_precision_ = int(kw.get("log_precision", 0))
         self.logs_ = []
         self.ctx = None
+        self.device_ = kw.get("device", 0)
         if isinstance(kernel, GaussianRBFKernel):
             self.ctx = Context(self.dimension_, coord.shape[1], device=kw.get("device", 0))
         elif not hasattr(opt, "Step"):
@@ -967,6 +984,28 @@ class SVGD:
         X = c.get_particles()
         self.coord_matrix_[...] = X.T
         self._write_logs()
+
+    def ComputeKSD(self, unbiased=False):
+        """KSD² of the caller's coordinate matrix against the model (extension):
+        the V-statistic, or the U-statistic when unbiased.  The RBF scale is
+        the kernel's own for an isotropic ScaleMethod.Constant, else
+        ln N / med² of the current particles.  The generic host-kernel path
+        opens a context on the configured device for the call."""
+        P = np.ascontiguousarray(np.asarray(self.coord_matrix_, dtype=np.float64).T)
+        G = self.model_.log_model_grad(P)
+        k = self.kernel_
+        a = None
+        if (isinstance(k, GaussianRBFKernel) and k.scale_matrix_ is None
+                and k.scale_method_ == GaussianRBFKernel.ScaleMethod.Constant):
+            a = k.scale_
+        c = self.ctx if self.ctx is not None else Context(P.shape[1], P.shape[0], device=self.device_)
+        try:
+            c.set_particles(P)
+            v, u = c.ksd(G[c.row0:c.row1], a)
+        finally:
+            if c is not self.ctx:
+                c.close()
+        return u if unbiased else v
 
     # -- generic kernel: the reference's ComputePhi on the host (SVGD.hpp:373-454)
     def _host_step(self, it):

@@ -407,6 +407,7 @@ struct svgd_ctx {
     int trk_nerrc = 0;
     double trk_pq = -1, trk_pc = -1; // this step's two extrapolations (< 0: none)
     double trk_dens = 0;        // candidates per unit of D^2 in the last bracket (all ranks)
+    double trk_gap = 0;         // (upper - lower selected D^2) / lower of the last selection
     double trk_pred = -1;       // this step's predicted median D^2 (< 0: sampled bracket)
     bool trk_go = false;        // this step's bracket is the predicted one (trk_plan)
     uint64_t trk_lo = 0, trk_hi = 0;
@@ -853,6 +854,10 @@ void trk_record(svgd_ctx *c, uint64_t lo_key, uint64_t hi_key, uint64_t cand)
     const double lo = key_value(lo_key);
     const double hi = hi_key >= 0x7ff0000000000000ull ? INFINITY : key_value(hi_key);
     c->trk_dens = (std::isfinite(hi) && hi > lo) ? (double)cand / (hi - lo) : 0.0;
+    // the averaged upper statistic: next to the lower one (1e-9 m at cfg3),
+    // or across a gap of the distance list (two equal clusters, even n)
+    const double m_hi = key_value(c->h_trk[5]);
+    c->trk_gap = m_hi > m && std::isfinite(m_hi) ? (m_hi - m) / m : 0.0;
     c->trk_m[3] = c->trk_m[2];
     c->trk_m[2] = c->trk_m[1];
     c->trk_m[1] = c->trk_m[0];
@@ -885,9 +890,15 @@ bool trk_predict(svgd_ctx *c, double Mq, double band_samp, uint64_t *lo_key, uin
         }
     }
     const double w = std::max(wp, c->trk_min_w);
-    const double band = c->trk_dens * (2.0 * w * pred) / Mq;
-    if (!(w < 0.05)) return false;
-    const double lo = pred * (1.0 - w), hi = pred * (1.0 + w);
+    // the bracket has to hold both averaged statistics: the prediction follows
+    // the lower one, the upper one lay trk_gap above it.  Across a gap of the
+    // list (two equal clusters, even n: the largest distance inside a cluster
+    // and the smallest between the two) they move independently and no
+    // extrapolation of the lower one places the upper one -- a bracket around
+    // the lower one alone missed on every step, each redone: sample instead.
+    if (!(w < 0.05) || !(c->trk_gap < 0.05)) return false;
+    const double lo = pred * (1.0 - w), hi = pred * (1.0 + c->trk_gap) * (1.0 + w);
+    const double band = c->trk_dens * (hi - lo) / Mq;
     if (!(band <= band_samp)) return false;
     *lo_key = __builtin_bit_cast(uint64_t, lo);
     *hi_key = __builtin_bit_cast(uint64_t, hi) + 1;

@@ -24,14 +24,19 @@ def run(rank, world, name, n, d, steps, q, env=None):
         from svgdcpp_amd import _capi as C
 
         X0 = O.splitmix((n, d), 3.0, 41)
+        upper = np.full(d, 2.5)
         if os.environ.get("SVGD_TEST_OUTLIERS"):  # far particles: a log2e max|xc|^2 > 300
             X0[:3] += float(os.environ["SVGD_TEST_OUTLIERS"])
+        if os.environ.get("SVGD_TEST_CLUSTERS"):  # "L,frac": the first round(frac n) rows move L along x_0
+            L, frac = (float(v) for v in os.environ["SVGD_TEST_CLUSTERS"].split(","))
+            X0[:int(round(frac * n)), 0] += L
+            upper[0] += L  # the clamp leaves the far cluster where it is
         mus = O.splitmix((3, d), 3.0, 42)
         covs = [np.eye(d) * (1.0 + 0.25 * c) for c in range(3)]
         ctx = S.Context(d, n, device=0, world=world, rank=rank)
         ctx.set_particles(X0)
         ctx.set_optimizer(C.SVGD_OPT_ADAM, 0.05, 0.9, 0.999, 1e-8)
-        ctx.set_bounds(-np.full(d, 2.5), np.full(d, 2.5))
+        ctx.set_bounds(-np.full(d, 2.5), upper)
         model = S.GaussianSum(list(mus), list(covs))
         scales = []
         ctx.diagnostics()

@@ -219,6 +219,34 @@ def test_sharded_symmetric_phi_hands_over_to_row_stream():
         np.testing.assert_allclose(X, X1, rtol=0, atol=1e-10)
 
 
+@pytest.mark.parametrize("sym", [None, "1"], ids=["phi-default", "phi-sym"])
+@pytest.mark.parametrize("world,n,clusters", [(2, 3000, "40,0.5"), (3, 6007, "40,0.6")])
+def test_sharded_step_on_two_clusters(world, n, clusters, sym):
+    """Two clusters 40 apart along x_0 (SVGD_TEST_CLUSTERS), the rows sorted
+    by cluster: one rank's pair tiles are all within a cluster, another's
+    mostly between the two, and at (2, 3000) the two averaged order statistics
+    come from either side of the gap, found from all-reduced counts.  With
+    the default phi and with the sharded symmetric pass, against one rank on
+    its default phi: the bars of test_sharded_step_matches_single_rank."""
+    d, steps = 5, 4
+    env = {"SVGD_TEST_CLUSTERS": clusters, "SVGD_DEBUG_COLL": "1"}
+    if sym is not None:
+        env["SVGD_PHI_SYM"] = sym
+    diags = {}
+    multi = _run_ranks(world, n, d, steps, env, diags=diags)
+    single = _run_ranks(1, n, d, steps, {"SVGD_TEST_CLUSTERS": clusters})[0]
+    X1, s1, _ = single
+    print("clusters %s world=%d n=%d one-rank scales %s" % (clusters, world, n, s1))
+    for rank, (X, scales, _) in multi.items():
+        assert diags[rank]["phi_kernel"].startswith("k_phi_sym" if sym else "k_phi_rows"), diags[rank]
+        assert scales[0][0] == s1[0][0], (rank, scales, s1)
+        np.testing.assert_allclose([s[0] for s in scales], [s[0] for s in s1], rtol=1e-13)
+        np.testing.assert_allclose(X, X1, rtol=0, atol=1e-10)
+    Xs = [multi[r][0] for r in range(world)]
+    assert all(np.array_equal(Xs[0], x) for x in Xs[1:])
+    assert len({tuple(s[0] for s in multi[r][1]) for r in range(world)}) == 1
+
+
 def test_measurement_context_refuses_results():
     """svgd_create_sim (bench.py --sim-world): rank 0's share of a P-rank step,
     measurement only -- it steps, but every call that hands results back

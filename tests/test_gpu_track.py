@@ -54,6 +54,44 @@ def test_tracked_brackets_bit_identical(oracle, monkeypatch, n, d, dtype):
     b.close()
 
 
+def test_no_predicted_bracket_across_a_gap(oracle, monkeypatch):
+    """Two equal clusters 40 apart, even n: the two averaged order statistics
+    are the largest distance inside a cluster and the smallest between the
+    two.  They move independently, so a bracket predicted from the lower one
+    cannot place the upper one: before the tracker looked at the upper
+    statistic, every tracked step of this run missed and was redone (8 of 8).
+    Now such steps sample their bracket: no misses, the same trajectory."""
+    import _clouds as K
+
+    n, d = 6000, 8
+    X = K.cloud("bal", n, d, K.seed_of("bal", n, d))
+    mus = np.zeros((2, d))
+    mus[0, 0] = K.split("bal", n)[1]
+    model = S.GaussianSum(list(mus), [np.eye(d), np.eye(d)])
+    ctxs = []
+    for tr in ("1", "0"):
+        monkeypatch.setenv("SVGD_TRACK_BRACKET", tr)
+        c = S.Context(d, n)
+        c.set_particles(X)
+        c.set_optimizer(C.SVGD_OPT_ADAM, 0.1, 0.9, 0.999, 1e-8)
+        ctxs.append(c)
+    a, b = ctxs
+    a.diagnostics()
+    for step in range(14):
+        for c in (a, b):
+            c.step_with_model(model)
+        assert np.array_equal(a.get_particles(), b.get_particles()), step
+        assert a.last_scale()[:2] == b.last_scale()[:2], step
+        s_lo, s_hi, _, _ = a.last_median_keys()
+        assert s_lo < (20.0 ** 2) < s_hi, (step, s_lo, s_hi)  # still either side of the gap (L / 2 = 20)
+    da = a.diagnostics()
+    print("track gap: trk_steps=%d trk_miss=%d spec_steps=%d" % (da["trk_steps"], da["trk_miss"], da["spec_steps"]))
+    assert da["spec_steps"] >= 10
+    assert da["trk_miss"] == 0
+    a.close()
+    b.close()
+
+
 def test_tracked_misses_are_redone(oracle, monkeypatch):
     """A half-width far below the median's step-to-step motion: every
     predicted bracket misses, each such step is redone with a sampled bracket,

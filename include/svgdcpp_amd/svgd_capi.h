@@ -247,7 +247,10 @@ int svgd_get_timing(svgd_ctx *ctx, double *phi_ms, double *median_ms, int64_t *c
 int svgd_get_diagnostics(svgd_ctx *ctx, double *out, int cap);
 /* Name and template arguments of the phi kernel this context launches, as
  * rocprofv3 prints them (e.g. "k_phi_rows<8, 4, 8, 8192, 8>"): the key under
- * which committed PMC profiles of that kernel are matched (bench.py). */
+ * which committed PMC profiles of that kernel are matched (bench.py).  The
+ * kernel is planned at creation (svgd_plan_phi_name gives the same answer
+ * without a context); a full-matrix scale set afterwards does not change the
+ * name, which stays the isotropic-scale kernel's. */
 int svgd_phi_kernel_name(const svgd_ctx *ctx, char *buf, int cap);
 /* Median tuning knobs (tests force each path): pair count at or below which
  * all keys are stored (direct path), sample size, candidate capacity.
@@ -318,6 +321,11 @@ int svgd_ksd(svgd_ctx *ctx, const double *G_shard, double a, double *ksd2_v, dou
 /* Row shard of rank r among `world` for n particles: equal chunks of
  * ceil(n/world) rows (trailing ranks may be short or empty). */
 void svgd_plan_rows(int64_t n, int world, int rank, int64_t *row0, int64_t *row1);
+/* The name svgd_phi_kernel_name reports for a context of `rank` among
+ * `world` created with these arguments under the current environment (the
+ * SVGD_PHI_* knobs): the same plan, made without a context or a GPU.
+ * SVGD_ERR_DIM above dimension 64. */
+int svgd_plan_phi_name(int dim, int64_t n, int dtype, int world, int rank, char *buf, int cap);
 /* Full-list ranks of the median (GaussianRBFKernel.hpp:222-254 over the n^2
  * distance list incl. n diagonal zeros) mapped onto the ascending list of
  * the n(n-1)/2 upper-triangle distances.  Writes up to two upper-list ranks

@@ -658,6 +658,16 @@ class SVGDOptions:
         self.Device = 0
 
 
+def plan_phi_name(dim, n, dtype=None, world=1, rank=0):
+    """The phi kernel (name<template args>) a context created with these
+    arguments would launch under the current environment: svgd_plan_phi_name,
+    the plan behind Context.phi_kernel_name() without a context or a GPU."""
+    buf = ctypes.create_string_buffer(128)
+    dt = C.SVGD_F64 if dtype is None else int(dtype)
+    _raise(None, C.lib().svgd_plan_phi_name(int(dim), int(n), dt, int(world), int(rank), buf, 128))
+    return buf.value.decode()
+
+
 class Context:
     """Owns one svgd_ctx (one GPU).  Thin RAII wrapper used by SVGD and the bench."""
 

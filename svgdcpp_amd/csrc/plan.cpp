@@ -16,8 +16,124 @@
 // ranks.
 #include <limits.h>
 #include <stdint.h>
+#include <stdio.h>
 
 #include "../../include/svgdcpp_amd/svgd_capi.h"
+#include "plan.h"
+
+namespace svgd_amd {
+
+bool pick_tiles(int d, int *KP, int *NCB)
+{
+    struct {
+        int maxd, kp, ncb;
+    } tab[] = {{4, 4, 1},   {8, 8, 1},   {12, 12, 1}, {15, 16, 1}, {16, 16, 2},
+               {31, 32, 2}, {32, 32, 3}, {63, 64, 4}, {64, 64, 5}};
+    for (auto &e : tab)
+        if (d <= e.maxd) {
+            *KP = e.kp;
+            *NCB = e.ncb;
+            return true;
+        }
+    return false;
+}
+
+// Which phi kernel a context runs, decided once (svgd_capi.cpp allocates for
+// it, run_phi launches it, svgd_phi_kernel_name prints it):
+//   fp64 d <= 16: the row stream, or the symmetric pass where it pays
+//   fp64 d > 16:  the fp64 tile kernel
+//   F32:          k_phi_b3 (KP 32 / 64) or k_phi_f32s (KP 16) on 16-aligned
+//                 rows, else the generic fp32 tile kernel
+bool plan_phi(int dim, int64_t n, int dtype, int plan_world, int64_t row0, const Knobs &k,
+              const PhiCaps &cap, PhiPlan *p)
+{
+    *p = PhiPlan{};
+    p->dim = dim;
+    if (dim <= 0 || !pick_tiles(dim, &p->KP, &p->NCB)) return false;
+    const bool f32 = dtype == SVGD_F32;
+    const bool rows = !f32 && cap.rows_kp > 0;
+    // row stream: xc rows are the median records [xc | |xc|^2 | 0..]
+    if (rows) p->KP = cap.rows_kp;
+    // F32: the phi on the bf16 matrix cores where it applies (SVGD_PHI_B3=0:
+    // the fp32-MFMA kernel k_phi_f32s)
+    const bool b3 = f32 && cap.b3 && !k.phi_tile_generic && k.phi_b3.or_(1);
+    // fp64 tiles and the bf16 F32 phi with d = 16 NCB: no V column of ones
+    // (row sums on the VALU); SVGD_PHI_S1V=0 keeps the ones column (A/B knob)
+    p->s1v = (!f32 || b3) && cap.tile_s1v && k.phi_s1v.or_(1);
+    if (p->s1v) p->NCB = dim / 16;
+    p->VW = 16 * p->NCB;
+    // k_phi_b3 with one 16-row group per wave, or two (SVGD_PHI_B3_RG=2:
+    // half its LDS reads and barriers per MFMA, a measured wash at cfg5 on the
+    // power-limited chip, profiles/r06_b3_rg_il_ab.txt)
+    if (b3) p->b3_rg = k.phi_b3_rg.or_(1);
+    if (rows) {
+        p->R = phi_rows_per_lane(dim);
+        // 8-wave work-groups, 8192-entry table, columns split over the waves
+        // (kind 2); the 4-wave kernel (kind 0) serves the full-matrix scales
+        // (signature rows) and an R the 8-wave build does not have
+        p->rows_kind = cap.rows_t8k ? 2 : 0;
+        // symmetric phi pass: isotropic scales, d <= 8 (a pair feeds two
+        // particles).  One rank: default since round 5 from N = 32768 up (with 16-byte record reads
+        // cfg3 phi 3.59 -> 3.08 ms, step 4.12 -> 3.68 ms, cfg4 65.5 -> 56.5
+        // ms; at cfg2, N = 16384, its extra launches outweigh the saving,
+        // 0.200 vs 0.265 ms -- profiles/r05_sym_ab.txt.  SVGD_PHI_SYM=1 / 0
+        // forces it on / off)
+        // P > 1: rank r runs the units [U r / P, U (r+1) / P), sums every
+        // particle's partials from them and a point-to-point exchange hands
+        // each rank the pieces of its rows (sym_exchange).  Its phi saving
+        // grows as N^2 / P, the exchange as N.  Round 5 (a reduce-scatter of
+        // all N (d+1) sums, units not balanced at P = 8): default from N / P >=
+        // 16384 (cfg3 shares P = 2 2.008 -> 1.875 ms, P = 4 1.066 -> 1.003, P =
+        // 8 0.587 -> 0.582; cfg4 P = 8 7.92 -> 6.84 ms, profiles/r05_sim_sym.txt,
+        // r05_cfg4_sim8_sym.txt).  Round 6: the padding-only sub-tiles left out
+        // of the units (11 per work-group at cfg3 P = 8 instead of 11 or 12) and
+        // ~2.5 MB sent per rank at cfg3 P = 8 instead of 4.1 MB in ring steps:
+        // default from N / P >= 8192 (cfg3 at P = 8 included)
+        const bool sym = cap.sym && (k.phi_sym.set ? k.phi_sym.v != 0
+                                                   : n >= 32768 && n / (plan_world < 1 ? 1 : plan_world) >= 8192);
+        p->path = sym ? PHI_SYM : PHI_ROWS;
+    } else if (!f32) {
+        p->path = PHI_TILE_F64;
+    } else {
+        // the streamed kernels' waves own 16-row groups of the padded rows: a
+        // shard that starts elsewhere takes the generic kernel
+        const bool streamed = cap.f32s && !k.phi_tile_generic && row0 % 16 == 0;
+        p->path = !streamed ? PHI_TILE_F32 : b3 ? PHI_B3 : PHI_F32S;
+    }
+    return true;
+}
+
+void phi_plan_name(const PhiPlan &p, const PhiCaps &cap, char *buf, int len)
+{
+    const char *const tf[] = {"false", "true"};
+    switch (p.path) {
+    case PHI_SYM:
+        snprintf(buf, (size_t)len, "k_phi_sym<%d>", p.dim);
+        break;
+    case PHI_ROWS:
+        // <D, R, NW, TABN, WC>.  Kind 2: T8K_NW waves, the 8192-entry table,
+        // T8K_WC column groups; kind 0: the template's defaults, 4 waves,
+        // EXP_TB = 4096 entries, 1.  These constants of svgd_kernels.hip have
+        // no accessor, so they are mirrored here.
+        snprintf(buf, (size_t)len, "k_phi_rows<%d, %d, %s>", p.dim, p.R,
+                 p.rows_kind == 2 ? "8, 8192, 8" : "4, 4096, 1");
+        break;
+    case PHI_B3:
+        snprintf(buf, (size_t)len, "k_phi_b3<%d, %d, %d, %s, %d>", p.KP, p.NCB, cap.b3_waves, tf[p.s1v],
+                 p.b3_rg);
+        break;
+    case PHI_F32S:
+        snprintf(buf, (size_t)len, "k_phi_f32s<%d, %d>", p.KP, p.NCB);
+        break;
+    case PHI_TILE_F32:
+    case PHI_TILE_F64:
+        snprintf(buf, (size_t)len, "k_phi<%s, %d, %d, %d, %s, %s>", p.path == PHI_TILE_F64 ? "double" : "float",
+                 p.KP, p.NCB, cap.tile_waves, tf[cap.tile_pre], tf[p.s1v]);
+        break;
+    }
+}
+
+} // namespace svgd_amd
 
 extern "C" {
 

@@ -28,6 +28,7 @@
 
 #include "../../include/svgdcpp_amd/svgd_capi.h"
 #include "svgd_kernels.h"
+#include "plan.h"
 #include "svgd_ksd.h"
 #include "hostcomm.h"
 #include "host_models.h"
@@ -152,7 +153,6 @@ struct svgd_ctx {
     ncclComm_t gcomm = nullptr;
     int coll_phase = 0;      // 0 step not begun, 1 scale_begin's comm calls issued, 2 G gathered
     uint64_t coll_sig = 0;   // FNV hash of this step's collectives (communicator, op, count)
-    bool dbg_coll = false;   // SVGD_DEBUG_COLL
     uint64_t *sig_buf = nullptr; // world u64 (the debug all-gather)
     hipStream_t gstream = nullptr;
     hipEvent_t ev_gg = nullptr;   // G all-gathered (gstream)
@@ -162,7 +162,8 @@ struct svgd_ctx {
     int dm_k = 0;
     double *dm_mu = nullptr, *dm_prec = nullptr;
     int64_t row0 = 0, row1 = 0, nrows = 0, chunk = 0;
-    int KP = 0, NCB = 0, VW = 0;
+    Knobs knobs;  // the environment, read once at creation (read_knobs)
+    PhiPlan plan; // the phi kernel of this context and its launch parameters (plan_phi)
     int64_t nb = 0, np = 0; // row blocks; padded rows of the work arrays
     hipStream_t stream = nullptr;
 
@@ -184,10 +185,9 @@ struct svgd_ctx {
     float *XS = nullptr, *VS = nullptr; // operand-ordered column copies (k_phi_f32s)
     uint32_t *B3 = nullptr;             // operand-ordered bf16 parts (k_phi_b3), replaces XS / VS
     uint32_t *XK = nullptr;             // F32 median key parts, KP 32 / 64 (svgd_device.h)
-    bool want_b3 = false;               // F32 phi on the bf16 matrix cores (init)
-    int b3_rg = 1;                      // k_phi_b3's row groups per wave (init)
 
-    // row-stream path (d <= ROWS_MAX_D)
+    // row-stream path (d <= ROWS_MAX_D): plan.rows(), which the median's
+    // kernels follow too
     bool rowpath = false;
     int RS = 0;             // record stride 2d+2
     double *rec = nullptr;  // np x RS particle records
@@ -203,10 +203,7 @@ struct svgd_ctx {
     int64_t split_h = 0;
     int S2 = 0, S2b = 0;
     hipEvent_t ev_xhalf = nullptr;
-    int R = 2; // rows per lane of k_phi_rows
-    int phi_kind = 0; // 0 k_phi_rows (4 waves: matrix scales), 2 k_phi_rows (8 waves, column-split)
-    // symmetric phi pass (k_phi_sym, one rank, d <= 8): geometry and buffers
-    bool sym = false;
+    // symmetric phi pass (k_phi_sym, d <= 8; plan.path == PHI_SYM): geometry and buffers
     int symB = 0, symSRS = 0, symNSUB = 0, sym_grid = 0;
     int64_t sym_nb = 0, sym_units = 0, sym_u0 = 0, sym_u1 = 0; // all units, this rank's [u0, u1)
     int sym_fS = 1; // the row stream's column splits when it takes the step (symok = 0)
@@ -239,7 +236,6 @@ struct svgd_ctx {
     bool shard_sample = false;
     int64_t collect_blocks = 1024; // collect-pass work-groups (4 per CU resident; 5 for the bf16-split mcol)
     bool mcol = true;              // bracket collect on the matrix cores (k_pair_mcol / _tcol)
-    bool mcol_bf16 = true;         // k_pair_mcol's Gram as split bf16 (d <= 8; SVGD_MCOL_BF16=0: f32)
     uint32_t *xsplit = nullptr;    // its operands, [hi | lo] bf16 x 8 per particle (the centring writes them)
     double band_est = 1.0;         // this step's bracket: expected share of the pairs
     bool samp_shard = false;    // this step's sample is sharded
@@ -360,7 +356,6 @@ struct svgd_ctx {
     // checked before the next call that depends on the step; a failed plan
     // (bracket miss, overflow, big buckets) restores X, m, v, t from the
     // backups and redoes the step on the synchronous path.
-    bool spec_allowed = true;  // SVGD_SPECULATE=0 disables
     bool spec_step = false;    // this step's median is speculative
     bool med_ev_done = false;  // this step's median end event is recorded
     // OpenMP threads of the host gradient inside svgd_step_host_model: half the
@@ -396,7 +391,6 @@ struct svgd_ctx {
     // radix passes.  The selection stays exact; a bracket that misses the order
     // statistics is a failed plan, and the step is redone with a sample.
     bool trk_allowed = true;    // SVGD_TRACK_BRACKET=0 disables
-    double trk_min_w = 2e-5;    // SVGD_TRACK_MIN_WIDTH: relative half-width floor
     double trk_err_mult = 4.0;  // SVGD_TRACK_ERR_MULT: half-width / recent error (set at creation)
     uint64_t *h_trk = nullptr, *h_trk_dev = nullptr; // pinned [lo, hi, below, cand, key0, key1, err]
     double trk_m[4] = {0, 0, 0, 0}; // last selected D^2 (lower order statistic), newest first
@@ -489,21 +483,6 @@ int fail(svgd_ctx *c, int code, const std::string &msg)
         int rc_ = (expr);                                                                       \
         if (rc_ != SVGD_OK) return rc_;                                                         \
     } while (0)
-
-bool pick_tiles(int d, int *KP, int *NCB)
-{
-    struct {
-        int maxd, kp, ncb;
-    } tab[] = {{4, 4, 1},   {8, 8, 1},   {12, 12, 1}, {15, 16, 1}, {16, 16, 2},
-               {31, 32, 2}, {32, 32, 3}, {63, 64, 4}, {64, 64, 5}};
-    for (auto &e : tab)
-        if (d <= e.maxd) {
-            *KP = e.kp;
-            *NCB = e.ncb;
-            return true;
-        }
-    return false;
-}
 
 template <class T> int dalloc(svgd_ctx *c, T **p, int64_t count)
 {
@@ -725,8 +704,8 @@ int center(svgd_ctx *c, const SelState *st_init = nullptr)
     const int ps = (int)((v - 1) & 1), cs = (int)(v & 1);
     const bool have = c->cpart && c->cpart_ver[ps] == v - 1;
     // F32 at KP 32 / 64: the centring writes the fp32 copies itself
-    const bool fused = c->dtype == SVGD_F32 && !c->rowpath && (c->KP == 32 || c->KP == 64);
-    HIPCHK(c, launch_mean_center(c->X, c->n, c->dim, c->KP, c->np, c->partial, c->nparts, c->xc, c->nrm,
+    const bool fused = c->dtype == SVGD_F32 && !c->rowpath && (c->plan.KP == 32 || c->plan.KP == 64);
+    HIPCHK(c, launch_mean_center(c->X, c->n, c->dim, c->plan.KP, c->np, c->partial, c->nparts, c->xc, c->nrm,
                                  c->rowpath ? 1 : 0, c->xf, nmax_cur(c), c->cnt3 + 3, c->stream, c->st,
                                  st_init, have ? c->cpart + ps * c->cpart_stride : nullptr,
                                  have ? c->cpart_n[ps] : 0, c->cpart ? c->cpart + cs * c->cpart_stride : nullptr,
@@ -738,10 +717,10 @@ int center(svgd_ctx *c, const SelState *st_init = nullptr)
     }
     if (c->dtype == SVGD_F32) {
         if (!fused) {
-            HIPCHK(c, launch_cvt_f32(c->xc, c->np * c->KP, c->xcf, c->stream));
+            HIPCHK(c, launch_cvt_f32(c->xc, c->np * c->plan.KP, c->xcf, c->stream));
             HIPCHK(c, launch_cvt_nrm_f32(c->nrm, c->n, c->np, c->nrmf, c->stream));
         }
-        if (c->XK) HIPCHK(c, launch_swz_keys_b3(c->xcf, c->KP, c->np, c->XK, c->stream));
+        if (c->XK) HIPCHK(c, launch_swz_keys_b3(c->xcf, c->plan.KP, c->np, c->XK, c->stream));
     }
     return SVGD_OK;
 }
@@ -787,15 +766,15 @@ hipError_t pair_pass(svgd_ctx *c, int mode, int grid, uint64_t *regions, int64_t
     // the collect pass (mode 0) also histograms its candidates in key-range buckets
     uint32_t *bp = mode == 0 ? c->bpart : nullptr;
     if (c->rowpath)
-        return launch_pair_rows(c->dim, c->KP, mode, grid, c->xc, c->nrm, c->xf, nmax_cur(c), c->n,
+        return launch_pair_rows(c->dim, c->plan.KP, mode, grid, c->xc, c->nrm, c->xf, nmax_cur(c), c->n,
                                 c->pnb, c->tile0,
                                 c->tile0 + c->own_tiles, regions, cap, c->counts, c->below, c->st,
                                 c->ghist, bp, dbg, c->stream);
     if (c->dtype == SVGD_F32)
-        return launch_pair_tiles_f32(c->KP, mode, grid, c->xcf, c->nrmf, c->n, c->pnb, c->tile0,
+        return launch_pair_tiles_f32(c->plan.KP, mode, grid, c->xcf, c->nrmf, c->n, c->pnb, c->tile0,
                                      c->tile0 + c->own_tiles, regions, cap, c->counts, c->below,
                                      c->st, c->ghist, bp, dbg, c->XK, c->stream);
-    return launch_pair_tiles(c->KP, mode, grid, c->xc, c->nrm, c->n, c->pnb, c->tile0,
+    return launch_pair_tiles(c->plan.KP, mode, grid, c->xc, c->nrm, c->n, c->pnb, c->tile0,
                              c->tile0 + c->own_tiles, regions, cap, c->counts, c->below, c->st,
                              c->ghist, bp, dbg, c->stream);
 }
@@ -889,7 +868,7 @@ bool trk_predict(svgd_ctx *c, double Mq, double band_samp, uint64_t *lo_key, uin
             pred = c->trk_pc;
         }
     }
-    const double w = std::max(wp, c->trk_min_w);
+    const double w = std::max(wp, c->knobs.track_min_width.or_(2e-5)); // relative half-width floor
     // the bracket has to hold both averaged statistics: the prediction follows
     // the lower one, the upper one lay trk_gap above it.  Across a gap of the
     // list (two equal clusters, even n: the largest distance inside a cluster
@@ -1030,7 +1009,7 @@ int median_begin(svgd_ctx *c)
             c->sample_alloc = S;
         }
         if (tile_sample)
-            HIPCHK(c, launch_sample_tiles(c->KP, c->xc, c->nrm, c->xcf, c->nrmf, c->XK, n,
+            HIPCHK(c, launch_sample_tiles(c->plan.KP, c->xc, c->nrm, c->xcf, c->nrmf, c->XK, n,
                                           S / (TB * TB), c->sample_keys, c->stream));
         // sharded (P > 1, scattered pairs): rank r draws pairs [S r/P, S (r+1)/P)
         // of the one counter-based sequence and the bracket's histograms are
@@ -1047,7 +1026,7 @@ int median_begin(svgd_ctx *c)
         // 12 measured none at no cost (the band stays ~1 % of the pairs)
         const SelState init = sample_state(c, tile_sample ? 4.0 * c->bracket_sigma : c->bracket_sigma);
         if (!tile_sample)
-            HIPCHK(c, launch_sample_keys(c->xc, c->nrm, c->xf, n, c->dim, c->KP, g0, c->samp_local,
+            HIPCHK(c, launch_sample_keys(c->xc, c->nrm, c->xf, n, c->dim, c->plan.KP, g0, c->samp_local,
                                          c->sample_keys, init, c->st, c->stream));
         else
             HIPCHK(c, launch_set_state(init, c->st, c->stream));
@@ -1115,7 +1094,7 @@ int collect_counts(svgd_ctx *c)
                                    c->counts, c->below, c->st, c->bpart, c->xsplit, c->stream));
     else if (!c->rowpath && c->dtype == SVGD_F32 && c->mcol)
         // fp32 tile path: k_pair_tiles' keys, rows held in VGPRs, no LDS
-        HIPCHK(c, launch_pair_tcol(c->KP, c->collect_grid, c->xcf, c->nrmf, c->XK, c->n, c->pnb,
+        HIPCHK(c, launch_pair_tcol(c->plan.KP, c->collect_grid, c->xcf, c->nrmf, c->XK, c->n, c->pnb,
                                    c->tile0, c->tile0 + c->own_tiles, c->regions, c->reg_cap,
                                    c->counts, c->below, c->st, c->bpart, c->stream));
     else
@@ -1395,12 +1374,6 @@ bool matrix_scale(const svgd_ctx *c)
     return c->scale_method == SVGD_SCALE_MATRIX || c->scale_method == SVGD_SCALE_HESSIAN;
 }
 
-// F32 with the streamed tile phi (operand-ordered copies allocated, 16-aligned rows)
-bool phi_streamed(const svgd_ctx *c)
-{
-    return c->dtype == SVGD_F32 && (c->XS || c->B3) && c->row0 % 16 == 0;
-}
-
 int run_phi(svgd_ctx *c, const OptArgs *opt)
 {
     // phi phase: the record preparation (V = G - 2a xc, part of the
@@ -1427,7 +1400,13 @@ int run_phi(svgd_ctx *c, const OptArgs *opt)
         c->gg_pending = false;
     }
     if (med_end) diag_end(c, c->stream, med_end, DG_PHI_WAIT, true);
+    // A matrix scale, chosen after the plan was made, modifies the planned
+    // launch per call: no symmetric pass, the 4-wave row kernel (kind 0:
+    // signature rows, sc_sgn), zc / zcf = L^T xc for xc / xcf, wv = 2 M xc.
+    const PhiPlan &p = c->plan;
     const bool mat = matrix_scale(c);
+    const PhiPath path = mat && p.path == PHI_SYM ? PHI_ROWS : p.path;
+    const int rows_kind = mat ? 0 : p.rows_kind;
     if (mat) {
         // M = factor * src, L = chol(M), a_eff = 1 (GaussianRBFKernel.hpp:189-210)
         const double factor = c->scale_method == SVGD_SCALE_HESSIAN
@@ -1436,7 +1415,7 @@ int run_phi(svgd_ctx *c, const OptArgs *opt)
         HIPCHK(c, launch_scale_factor(c->sc_src, factor, c->dim, c->sc_M, c->sc_L, c->sc_sgn,
                                       c->sc_work, c->scal, c->sc_err, c->stream));
         HIPCHK(c, hipMemcpyAsync(c->h_err, c->sc_err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        if (!c->rowpath) {
+        if (!p.rows()) {
             // the MFMA tile kernels need M positive definite: check before phi
             HIPCHK(c, hipStreamSynchronize(c->stream));
             if (*c->h_err == 2)
@@ -1444,50 +1423,51 @@ int run_phi(svgd_ctx *c, const OptArgs *opt)
                             "[Runtime Error] The kernel scale matrix is indefinite; the device "
                             "path supports indefinite matrices for fp64 particles with d <= 16 only.");
         }
-        if (*c->h_err == 1 && !c->rowpath)
+        if (*c->h_err == 1 && !p.rows())
             return fail(c, SVGD_ERR_RUNTIME, "[Runtime Error] The kernel scale matrix is not finite.");
-        if (c->rowpath)
+        if (p.rows())
             HIPCHK(c, launch_prep_rec_mat(c->xc, c->G, c->sc_M, c->sc_L, c->sc_sgn, c->n, c->np,
-                                          c->dim, c->KP, c->RS, c->rec, c->wv, c->stream));
+                                          c->dim, p.KP, c->RS, c->rec, c->wv, c->stream));
         else
-            HIPCHK(c, launch_prep_v_mat(c->xc, c->G, c->sc_M, c->sc_L, c->n, c->np, c->dim, c->KP,
-                                        c->VW, c->zc, c->V, c->cvec, c->wv, c->stream));
-    } else if (c->rowpath && !c->sym) // (the symmetric pass's prep writes these when it does not apply)
-        HIPCHK(c, launch_prep_rec(c->xc, c->G, c->nrm, c->scal, c->n, c->np, c->dim, c->KP, c->RS,
+            HIPCHK(c, launch_prep_v_mat(c->xc, c->G, c->sc_M, c->sc_L, c->n, c->np, c->dim, p.KP,
+                                        p.VW, c->zc, c->V, c->cvec, c->wv, c->stream));
+    } else if (path == PHI_ROWS) // (the symmetric pass's prep writes these when it does not apply)
+        HIPCHK(c, launch_prep_rec(c->xc, c->G, c->nrm, c->scal, c->n, c->np, c->dim, p.KP, c->RS,
                                   c->rec, c->stream));
-    else if (!c->rowpath)
-        HIPCHK(c, launch_prep_v(c->xc, c->G, c->nrm, c->scal, c->n, c->np, c->dim, c->KP, c->VW,
+    else if (!p.rows())
+        HIPCHK(c, launch_prep_v(c->xc, c->G, c->nrm, c->scal, c->n, c->np, c->dim, p.KP, p.VW,
                                 c->V, c->cvec, c->stream));
-    // F32: the streamed kernel's operand-ordered column copies (k_swz_f32), or
-    // the row-major fp32 copies of the generic tile kernel
-    const bool phis = phi_streamed(c);
+    // F32: the streamed kernels' operand-ordered column copies (k_swz_b3 /
+    // k_swz_f32), or the row-major fp32 copies of the generic tile kernel
     const int64_t ntl = (c->n + TBJ_COLS - 1) / TBJ_COLS;
     if (c->dtype == SVGD_F32) {
-        if (phis && c->B3)
-            HIPCHK(c, launch_swz_b3(mat ? c->zc : c->xc, c->KP, c->V, c->VW, c->cvec, c->n, ntl, c->B3,
+        if (path == PHI_B3)
+            HIPCHK(c, launch_swz_b3(mat ? c->zc : c->xc, p.KP, c->V, p.VW, c->cvec, c->n, ntl, c->B3,
                                     c->stream));
-        else if (phis)
-            HIPCHK(c, launch_swz_f32(mat ? c->zc : c->xc, c->KP, c->V, c->VW, c->cvec, ntl, c->XS,
+        else if (path == PHI_F32S)
+            HIPCHK(c, launch_swz_f32(mat ? c->zc : c->xc, p.KP, c->V, p.VW, c->cvec, ntl, c->XS,
                                      c->VS, c->stream));
         else
-            HIPCHK(c, launch_cvt_f32(c->V, c->np * c->VW, c->Vf, c->stream));
+            HIPCHK(c, launch_cvt_f32(c->V, c->np * p.VW, c->Vf, c->stream));
         HIPCHK(c, launch_cvt_f32(c->cvec, c->np, c->cvf, c->stream));
-        if (mat) HIPCHK(c, launch_cvt_f32(c->zc, c->np * c->KP, c->zcf, c->stream));
+        if (mat) HIPCHK(c, launch_cvt_f32(c->zc, c->np * p.KP, c->zcf, c->stream));
     }
     // level 2: the phi kernel alone (k_phi_rows before its reduce, k_phi_sym,
     // or the tile kernel)
-    const bool sym = c->sym && !mat;
-    const bool split = c->split_rows && c->in_host_step && c->rowpath && !mat && !sym && opt;
+    const bool sym = path == PHI_SYM;
+    const bool split = path == PHI_ROWS && c->split_rows && c->in_host_step && !mat && opt;
     c->xhalf_ready = split;
     c->n_split += split ? 1 : 0;
     hipEvent_t k0 = sym ? (c->tlevel >= 2 ? take_ev(c) : nullptr) : diag_begin(c, c->stream);
     hipEvent_t k1 = k0 ? take_ev(c) : nullptr;
-    if (sym) {
+    const double inv_n = 1.0 / (double)c->n;
+    switch (path) {
+    case PHI_SYM: {
         c->mark = c->phi_end = nullptr;
-        SymArgs sa{c->dim,    c->xc,        c->KP,          c->G,        c->nrm,       c->scal,
+        SymArgs sa{c->dim,    c->xc,        p.KP,           c->G,        c->nrm,       c->scal,
                    nmax_cur(c),   c->n,         c->sym_nb,      c->sym_u0,   c->sym_u1,    c->srec,
                    c->symok,  c->rowpart,   c->colpart,     c->sym_grid, c->row0,
-                   c->nrows,  1.0 / (double)c->n, c->phi, c->rec, c->RS, c->contrib,
+                   c->nrows,  inv_n, c->phi, c->rec, c->RS, c->contrib,
                    c->sym_tab, c->sym_tab + 2 * c->sym_nb,
                    c->sym_SM, c->sym_Ia, c->sym_Ib, c->part, c->sym_fS, c->ldp,
                    c->sym_tab + 3 * c->sym_nb, c->sym_qlast, c->tab8k};
@@ -1503,48 +1483,56 @@ int run_phi(svgd_ctx *c, const OptArgs *opt)
             HIPCHK(c, launch_sym_apply(sa, c->contrib + (size_t)c->row0 * (c->dim + 1), c->xrecv_buf, c->xtab_d,
                                        c->xtab_d ? c->world : 1, c->xtab_d ? c->rank : 0, opt, c->stream));
         }
-    } else if (c->rowpath && split) {
-        // two row halves: the first half's X_{t+1} is final at ev_xhalf, while
-        // the second half's phi runs (svgd_step_host_model copies it down and
-        // starts its gradient there)
-        const int64_t h = c->split_h, d = c->dim;
-        OptArgs o1 = *opt, o2 = *opt;
-        o2.X += h * d;
-        o2.m += h * d;
-        o2.v += h * d;
-        if (o2.bak) o2.bak += h * d;
-        if (o2.xh) o2.xh += h * d;
-        HIPCHK(c, launch_phi_rows(c->dim, c->R, c->rec, c->scal, c->row0, h, c->n, c->S2, c->part, h,
-                                  1.0 / (double)c->n, nullptr, nullptr, nmax_cur(c), c->phi, &o1, c->stream, k1,
-                                  c->phi_kind));
-        HIPCHK(c, hipEventRecord(c->ev_xhalf, c->stream));
-        hipEvent_t k2 = diag_begin(c, c->stream);
-        hipEvent_t k3 = k2 ? take_ev(c) : nullptr;
-        HIPCHK(c, launch_phi_rows(c->dim, c->R, c->rec, c->scal, c->row0 + h, c->nrows - h, c->n, c->S2b,
-                                  c->part, c->nrows - h, 1.0 / (double)c->n, nullptr, nullptr, nmax_cur(c),
-                                  c->phi + h * d, &o2, c->stream, k3, c->phi_kind));
-        if (k2) c->ev_diag.push_back({k2, k3, DG_PHI_KERNEL, true});
-    } else if (c->rowpath) {
-        HIPCHK(c, launch_phi_rows(c->dim, c->R, c->rec, c->scal, c->row0, c->nrows, c->n, c->S, c->part,
-                                  c->ldp, 1.0 / (double)c->n, mat ? c->wv : nullptr,
-                                  mat ? c->sc_sgn : nullptr, mat ? nullptr : nmax_cur(c), c->phi, opt,
-                                  c->stream, k1, mat ? 0 : c->phi_kind));
-    } else if (phis)
-        HIPCHK(c, c->B3 ? launch_phi_b3(c->KP, c->NCB, c->B3, c->cvf, c->scal, c->row0, c->nrows, ntl,
-                                        c->dim, 1.0 / (double)c->n, mat ? c->wv : nullptr, c->xc, c->KP,
-                                        c->phi, opt, c->b3_rg, c->stream)
-                        : launch_phi_f32s(c->KP, c->NCB, c->XS, c->VS, mat ? c->zcf : c->xcf, c->cvf, c->scal,
-                                  c->row0, c->nrows, ntl, c->dim, 1.0 / (double)c->n,
-                                  mat ? c->wv : nullptr, c->xc, c->KP, c->phi, opt, c->stream));
-    else if (c->dtype == SVGD_F32)
-        HIPCHK(c, launch_phi_f32(c->KP, c->NCB, mat ? c->zcf : c->xcf, c->cvf, c->Vf, c->scal,
-                                 c->row0, c->nrows, (c->n + TB - 1) / TB, c->n, c->dim,
-                                 1.0 / (double)c->n, mat ? c->wv : nullptr, c->xc, c->phi,
-                                 c->stream));
-    else
-        HIPCHK(c, launch_phi(c->KP, c->NCB, mat ? c->zc : c->xc, c->cvec, c->V, c->scal, c->row0,
-                             c->nrows, (c->n + TB - 1) / TB, c->n, c->dim, 1.0 / (double)c->n,
-                             mat ? c->wv : nullptr, c->phi, c->stream));
+        break;
+    }
+    case PHI_ROWS:
+        if (split) {
+            // two row halves: the first half's X_{t+1} is final at ev_xhalf, while
+            // the second half's phi runs (svgd_step_host_model copies it down and
+            // starts its gradient there)
+            const int64_t h = c->split_h, d = c->dim;
+            OptArgs o1 = *opt, o2 = *opt;
+            o2.X += h * d;
+            o2.m += h * d;
+            o2.v += h * d;
+            if (o2.bak) o2.bak += h * d;
+            if (o2.xh) o2.xh += h * d;
+            HIPCHK(c, launch_phi_rows(c->dim, p.R, c->rec, c->scal, c->row0, h, c->n, c->S2, c->part, h,
+                                      inv_n, nullptr, nullptr, nmax_cur(c), c->phi, &o1, c->stream, k1,
+                                      rows_kind));
+            HIPCHK(c, hipEventRecord(c->ev_xhalf, c->stream));
+            hipEvent_t k2 = diag_begin(c, c->stream);
+            hipEvent_t k3 = k2 ? take_ev(c) : nullptr;
+            HIPCHK(c, launch_phi_rows(c->dim, p.R, c->rec, c->scal, c->row0 + h, c->nrows - h, c->n, c->S2b,
+                                      c->part, c->nrows - h, inv_n, nullptr, nullptr, nmax_cur(c),
+                                      c->phi + h * d, &o2, c->stream, k3, rows_kind));
+            if (k2) c->ev_diag.push_back({k2, k3, DG_PHI_KERNEL, true});
+        } else {
+            HIPCHK(c, launch_phi_rows(c->dim, p.R, c->rec, c->scal, c->row0, c->nrows, c->n, c->S, c->part,
+                                      c->ldp, inv_n, mat ? c->wv : nullptr, mat ? c->sc_sgn : nullptr,
+                                      mat ? nullptr : nmax_cur(c), c->phi, opt, c->stream, k1, rows_kind));
+        }
+        break;
+    case PHI_B3:
+        HIPCHK(c, launch_phi_b3(p.KP, p.NCB, c->B3, c->cvf, c->scal, c->row0, c->nrows, ntl, c->dim, inv_n,
+                                mat ? c->wv : nullptr, c->xc, p.KP, c->phi, opt, p.b3_rg, c->stream));
+        break;
+    case PHI_F32S:
+        HIPCHK(c, launch_phi_f32s(p.KP, p.NCB, c->XS, c->VS, mat ? c->zcf : c->xcf, c->cvf, c->scal,
+                                  c->row0, c->nrows, ntl, c->dim, inv_n, mat ? c->wv : nullptr, c->xc,
+                                  p.KP, c->phi, opt, c->stream));
+        break;
+    case PHI_TILE_F32:
+        HIPCHK(c, launch_phi_f32(p.KP, p.NCB, mat ? c->zcf : c->xcf, c->cvf, c->Vf, c->scal, c->row0,
+                                 c->nrows, (c->n + TB - 1) / TB, c->n, c->dim, inv_n,
+                                 mat ? c->wv : nullptr, c->xc, c->phi, c->stream));
+        break;
+    case PHI_TILE_F64:
+        HIPCHK(c, launch_phi(p.KP, p.NCB, mat ? c->zc : c->xc, c->cvec, c->V, c->scal, c->row0,
+                             c->nrows, (c->n + TB - 1) / TB, c->n, c->dim, inv_n, mat ? c->wv : nullptr,
+                             c->phi, c->stream));
+        break;
+    }
     if (k0) {
         if (!c->rowpath) HIPCHK(c, hipEventRecord(k1, c->stream));
         c->ev_diag.push_back({k0, k1, DG_PHI_KERNEL, true});
@@ -1568,7 +1556,7 @@ int coll_check_step(svgd_ctx *c)
     const uint64_t mine = c->coll_sig;
     c->coll_sig = 0;
     c->coll_phase = 0;
-    if (!c->dbg_coll || (!c->comm && !c->hcomm)) return SVGD_OK;
+    if (!c->knobs.debug_coll.or_(0) || (!c->comm && !c->hcomm)) return SVGD_OK;
     if (!c->sig_buf) {
         HIPCHK(c, hipMalloc((void **)&c->sig_buf, sizeof(uint64_t) * (size_t)c->world));
     }
@@ -1624,7 +1612,7 @@ int run_phi_opt(svgd_ctx *c)
         return fail(c, SVGD_ERR_ARG, "[Argument Error] Invalid Optimizer object pointer.");
     OptArgs o;
     CHK(opt_args(c, &o));
-    const bool fused = c->rowpath || phi_streamed(c);
+    const bool fused = c->plan.fused();
     c->phi_end = nullptr;
     c->xh_valid = false;
     CHK(run_phi(c, fused ? &o : nullptr));
@@ -1833,42 +1821,71 @@ int plan_step(svgd_ctx *c)
     int64_t cap = CAPR_MIN;
     while (cap < 2 * c->last_tot && cap < CAPG) cap <<= 1;
     c->spec_cap = std::min<int64_t>(cap, CAPG);
-    c->spec_step = c->spec_allowed && c->last_fast && c->scale_method == SVGD_SCALE_MEDIAN &&
+    c->spec_step = c->knobs.speculate.or_(1) && c->last_fast && c->scale_method == SVGD_SCALE_MEDIAN &&
                    c->bucket_cap >= c->spec_cap;
     if (c->spec_step && !c->bak) CHK(dalloc(c, &c->bak, 3 * std::max<int64_t>(1, c->nrows) * c->dim));
     c->n_spec += c->spec_step ? 1 : 0;
     return SVGD_OK;
 }
 
-int init_ctx(svgd_ctx *c, int dim, int64_t n, int dtype, int device, int sim_world = 1)
+// ------------------------------------------------------------- creation --
+
+// The environment, read once per context: every SVGD_* variable the library
+// knows is named here, next to its Knobs field, and nowhere else.  Parsing
+// only -- what an unset knob defaults to is decided where it is used.
+Knobs read_knobs()
 {
-    if (dim <= 0 || n <= 0)
-        return fail(c, SVGD_ERR_DIM, "[Dimension Error] Particle count and dimension must be positive.");
-    if (dtype != SVGD_F64 && dtype != SVGD_F32)
-        return fail(c, SVGD_ERR_ARG, "[Argument Error] dtype must be SVGD_F64 or SVGD_F32.");
-    const bool f32 = dtype == SVGD_F32;
-    if (!pick_tiles(dim, &c->KP, &c->NCB))
-        return fail(c, SVGD_ERR_DIM, "[Dimension Error] Device path supports dimension <= 64.");
-    // row-stream path (fp64, d <= 16): xc rows are the median records [xc | |xc|^2 | 0..]
-    if (dim <= ROWS_MAX_D && !f32) c->KP = med_rec_stride(dim);
-    // F32: the phi on the bf16 matrix cores (k_phi_b3) where it applies
-    // (SVGD_PHI_B3=0: the fp32-MFMA kernel k_phi_f32s)
-    c->want_b3 = false;
-    if (f32 && phi_b3_supported(c->KP, c->NCB) && !std::getenv("SVGD_PHI_TILE_GENERIC")) {
-        const char *e = std::getenv("SVGD_PHI_B3");
-        c->want_b3 = !e || std::atoi(e) != 0;
-    }
-    // fp64 tiles and the bf16 F32 phi with d = 16 NCB: no V column of ones
-    // (row sums on the VALU); SVGD_PHI_S1V=0 keeps the ones column (A/B knob)
-    if ((!f32 || c->want_b3) && phi_tile_s1v(dim)) {
-        const char *e = std::getenv("SVGD_PHI_S1V");
-        if (!e || std::atoi(e) != 0) c->NCB = dim / 16;
-    }
-    c->dim = dim;
-    c->n = n;
-    c->dtype = dtype;
-    c->device = device;
-    c->VW = 16 * c->NCB;
+    auto get = [](const char *name, auto parse, auto *knob) {
+        if (const char *e = std::getenv(name)) {
+            knob->set = true;
+            knob->v = parse(e);
+        }
+    };
+    auto onoff = [](const char *e) { return (int)(std::atoi(e) != 0); };
+    auto real = [](const char *e) { return std::atof(e); };
+    Knobs k;
+    k.phi_tile_generic = std::getenv("SVGD_PHI_TILE_GENERIC") != nullptr;
+    get("SVGD_PHI_B3", onoff, &k.phi_b3);
+    get("SVGD_PHI_S1V", onoff, &k.phi_s1v);
+    get("SVGD_PHI_B3_RG", [](const char *e) { return std::atoi(e) == 2 ? 2 : 1; }, &k.phi_b3_rg);
+    get("SVGD_PHI_SYM", [](const char *e) { return std::atoi(e); }, &k.phi_sym);
+    get("SVGD_PHI_SPLIT", onoff, &k.phi_split);
+    get("SVGD_PHI_SPLIT_FRAC", [](const char *e) { return std::min(90, std::max(10, std::atoi(e))); },
+        &k.phi_split_frac);
+    get("SVGD_X_MIRROR", onoff, &k.x_mirror);
+    get("SVGD_BUCKET_CAP", [](const char *e) { return (int64_t)std::atoll(e); }, &k.bucket_cap);
+    get("SVGD_MEDIAN_SAMPLE", [](const char *e) { return std::max<int64_t>(1, std::atoll(e)); },
+        &k.median_sample);
+    get("SVGD_MEDIAN_SIGMA", [](const char *e) { return std::max(0.0, std::atof(e)); }, &k.median_sigma);
+    get("SVGD_COLLECT_FP64", [](const char *e) { return (int)(std::atoi(e) == 0); }, &k.mcol);
+    get("SVGD_MCOL_BF16", onoff, &k.mcol_bf16);
+    get("SVGD_SPECULATE", onoff, &k.speculate);
+    get("SVGD_TRACK_BRACKET", onoff, &k.track_bracket);
+    get("SVGD_TRACK_MIN_WIDTH", real, &k.track_min_width);
+    get("SVGD_TRACK_ERR_MULT", real, &k.track_err_mult);
+    get("SVGD_HOST_THREADS", [](const char *e) { return std::max(1, std::atoi(e)); }, &k.host_threads);
+    get("SVGD_DEBUG_COLL", onoff, &k.debug_coll);
+    get("SVGD_G_COMM", onoff, &k.g_comm);
+    get("SVGD_HOSTCOMM", [](const char *e) { return std::string(e); }, &k.hostcomm);
+    return k;
+}
+
+// What the kernel translation unit has built for (dim, dtype)
+PhiCaps phi_caps(int dim, int dtype)
+{
+    int KP = 0, NCB = 0, nw = 0, pre = 0;
+    (void)pick_tiles(dim, &KP, &NCB);
+    phi_tile_cfg(dtype != SVGD_F32, &nw, &pre);
+    return PhiCaps{dim >= 1 && dim <= ROWS_MAX_D ? med_rec_stride(dim) : 0,
+                   phi_rows_t8k_supported(dim, phi_rows_per_lane(dim)), phi_sym_supported(dim),
+                   phi_tile_s1v(dim), phi_f32s_supported(KP, NCB), phi_b3_supported(KP, NCB),
+                   nw, pre != 0, phi_b3_rows_per_wg(1) / 16};
+}
+
+// Step 1: this rank's rows and its range of the median's pair tiles.
+void plan_rows_tiles(svgd_ctx *c, int sim_world)
+{
+    const int64_t n = c->n;
     c->nb = (n + TB - 1) / TB;
     c->np = c->nb * TB + TB;
     c->chunk = (n + c->world - 1) / c->world;
@@ -1883,18 +1900,10 @@ int init_ctx(svgd_ctx *c, int dim, int64_t n, int dtype, int device, int sim_wor
     c->plan_world = plan_world;
     svgd_plan_rows(n, plan_world, c->rank, &c->row0, &c->row1);
     c->nrows = c->row1 - c->row0;
-    // k_phi_b3 with one 16-row group per wave, or two (SVGD_PHI_B3_RG=2:
-    // half its LDS reads and barriers per MFMA, a measured wash at cfg5 on the
-    // power-limited chip, profiles/r06_b3_rg_il_ab.txt)
-    if (c->want_b3)
-        if (const char *e = std::getenv("SVGD_PHI_B3_RG")) c->b3_rg = std::atoi(e) == 2 ? 2 : 1;
-    c->pblock = SVGD_PAIR_BLOCK_DT(dim, dtype);
+    c->pblock = SVGD_PAIR_BLOCK_DT(c->dim, c->dtype);
     c->pnb = (n + c->pblock - 1) / c->pblock;
     c->own_tiles = svgd_plan_pair_tiles(n, c->pblock, plan_world, c->rank);
-    {
-        const int64_t T = c->pnb * (c->pnb + 1) / 2;
-        c->tile0 = T * c->rank / plan_world;
-    }
+    c->tile0 = c->pnb * (c->pnb + 1) / 2 * c->rank / plan_world;
     if (c->sim_world > 1) { // real pairs of the share's tiles (diagonal tiles: upper half)
         for (int64_t t = 0; t < c->own_tiles; ++t) {
             int64_t I, J;
@@ -1904,180 +1913,174 @@ int init_ctx(svgd_ctx *c, int dim, int64_t n, int dtype, int device, int sim_wor
             c->sim_pairs += I == J ? ri * (ri - 1) / 2 : ri * rj;
         }
     }
-    HIPCHK(c, hipSetDevice(device));
-    HIPCHK(c, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    HIPCHK(c, hipStreamCreateWithFlags(&c->cstream, hipStreamNonBlocking));
+}
+
+// The symmetric pass (plan.path == PHI_SYM): this rank's units, its tables and buffers.
+int setup_sym(svgd_ctx *c, int ncu)
+{
+    const int dim = c->dim;
+    const int64_t n = c->n;
+    if (!phi_sym_geom(dim, &c->symB, &c->symSRS, &c->symNSUB))
+        return fail(c, SVGD_ERR_DIM, "[Dimension Error] The symmetric phi pass has no geometry for this dimension.");
+    const int64_t B = c->symB;
+    c->sym_nb = (n + B - 1) / B;
+    c->sym_units = svgd_plan_sym_total(n, (int)B, c->symNSUB); // (no padding-only sub-tiles)
+    const int64_t Pw = c->plan_world, r = c->sim_world > 1 ? 0 : c->rank;
+    const int64_t slots = (int64_t)phi_sym_blocks_per_cu(dim) * ncu;
+    const int64_t Vr = c->sym_units * (r + 1) / Pw - c->sym_units * r / Pw;
+    c->sym_grid = (int)std::max<int64_t>(1, std::min<int64_t>(Vr, slots));
+    // the rank's units, the row blocks each work-group's contiguous run
+    // visits and each row block's contiguous row-sum records (plan.cpp)
+    const int64_t nbs = c->sym_nb;
+    std::vector<int> tab(3 * (size_t)nbs + 2 * (size_t)c->sym_grid);
+    int *blkg = tab.data(), *rbase = blkg + 2 * nbs, *wst = rbase + nbs;
+    const int64_t nrec = svgd_plan_sym_units(n, (int)B, c->symNSUB, (int)Pw, (int)r, c->sym_grid,
+                                             &c->sym_u0, &c->sym_u1, blkg, rbase, &c->sym_Ia, &c->sym_Ib);
+    // each work-group's first unit (the kernel advances from there)
+    for (int g = 0; g < c->sym_grid; ++g) {
+        const int64_t V = c->sym_u1 - c->sym_u0;
+        int64_t t = 0, q = 0;
+        svgd_plan_sym_unit(n, (int)B, c->symNSUB, c->sym_u0 + V * g / c->sym_grid, &t, &q);
+        wst[2 * g] = (int)t;
+        wst[2 * g + 1] = (int)q;
+    }
+    {
+        const int64_t sub = B / c->symNSUB, valid = n - (nbs - 1) * B;
+        c->sym_qlast = (int)((valid + sub - 1) / sub);
+    }
+    c->sym_SM = (nbs - 1) / 2 + 2;
+    // the row stream's hand-over inside k_phi_sym (symok = 0): its
+    // 8-wave work-groups, one wave of them (<= c->S, the part buffer's splits)
+    {
+        const int64_t rows_wg = phi_rows_t8k_rows(4);
+        const int64_t ib = std::max<int64_t>(1, (c->nrows + rows_wg - 1) / rows_wg);
+        c->sym_fS = (int)std::max<int64_t>(1, std::min<int64_t>(c->S, ncu / ib));
+    }
+    CHK(dalloc(c, &c->sym_tab, (int64_t)tab.size()));
+    HIPCHK(c, hipMemcpyAsync(c->sym_tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice,
+                             c->stream)); // (after dalloc's memset on the same stream)
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    CHK(dalloc(c, &c->srec, c->sym_nb * B * c->symSRS));
+    CHK(dalloc(c, &c->rowpart, nrec * B * (dim + 1)));
+    // zeroed here once: entries no unit of this rank writes stay zero
+    CHK(dalloc(c, &c->colpart, nbs * c->sym_SM * B * (dim + 1)));
+    CHK(dalloc(c, &c->symok, 1));
+    CHK(dalloc(c, &c->tab8k, 8192));
+    HIPCHK(c, launch_fill_tab8k(c->tab8k, c->stream));
+    // (SVGD_PHI_SYM=2, a test knob: the P > 1 form -- sums, exchange call site, apply -- at any P)
+    if (Pw > 1 || c->knobs.phi_sym.or_(-1) == 2)
+        CHK(dalloc(c, &c->contrib, std::max<int64_t>(c->np, c->world * c->chunk) * (dim + 1)));
+    if (c->world > 1) {
+        // the exchange plan: the same ranges on both sides of every pair of ranks
+        c->xsend.assign(2 * (size_t)c->world, 0);
+        c->xrecv.assign(3 * (size_t)c->world, 0);
+        for (int q = 0; q < c->world; ++q) {
+            int64_t a, b;
+            svgd_plan_sym_exchange(n, (int)B, c->symNSUB, c->world, c->rank, q, &a, &b);
+            c->xsend[2 * q] = a;
+            c->xsend[2 * q + 1] = q == c->rank ? a : b; // (its own rows: not sent)
+            svgd_plan_sym_exchange(n, (int)B, c->symNSUB, c->world, q, c->rank, &a, &b);
+            if (q != c->rank && b > a) {
+                c->xrecv[3 * q] = a;
+                c->xrecv[3 * q + 1] = b;
+                c->xrecv[3 * q + 2] = c->xrecv_rows;
+                c->xrecv_rows += b - a;
+            }
+        }
+        CHK(dalloc(c, &c->xrecv_buf, std::max<int64_t>(1, c->xrecv_rows) * (dim + 1)));
+        HIPCHK(c, hipMalloc((void **)&c->xtab_d, c->xrecv.size() * sizeof(int64_t)));
+        HIPCHK(c, hipMemcpy(c->xtab_d, c->xrecv.data(), c->xrecv.size() * sizeof(int64_t),
+                            hipMemcpyHostToDevice));
+    }
+    return SVGD_OK;
+}
+
+// The row stream's records, column splits and partials (+ the symmetric pass).
+int alloc_phi_rows(svgd_ctx *c)
+{
+    const PhiPlan &p = c->plan;
+    const int dim = c->dim;
+    const int64_t n = c->n;
+    int ncu = 256;
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, c->device) == hipSuccess) ncu = prop.multiProcessorCount;
+    // column splits of a launch over `rows` rows: enough work-groups to fill
+    // every CU at the kernel's occupancy, 2 blocks per resident slot: one
+    // block wave per slot left a tail of idle CUs (measured at cfg3, phi
+    // launch: S x1 4.00 ms, x2 3.83-3.93, x4 3.81-3.90, x8 3.91-3.95 -- x2
+    // and x4 tie, x2 has half the partials)
+    const int64_t resident = (int64_t)phi_rows_blocks_per_cu(dim, p.R, p.rows_kind) * ncu;
+    const int64_t rows_wg = p.rows_kind == 2 ? phi_rows_t8k_rows(p.R) : 256 * (int64_t)p.R;
+    auto splits = [&](int64_t rows) {
+        constexpr int split_mult = 2;
+        const int64_t ib = std::max<int64_t>(1, (rows + rows_wg - 1) / rows_wg);
+        const int64_t s = std::max<int64_t>(1, (resident + ib - 1) / ib) * split_mult;
+        return (int)std::min<int64_t>(s, std::max<int64_t>(1, n / 256));
+    };
+    c->S = splits(c->nrows);
+    c->RS = phi_rec_stride(dim);
+    c->ldp = std::max<int64_t>(1, c->nrows);
+    // two row parts (svgd_step_host_model at P > 1, split_rows policy in
+    // host_policy): the first part's rows get their X_{t+1} while the second
+    // part's phi still runs; the second part's gradient has to fit in the
+    // next step's median phase.  Each launch takes its own column splits.
+    // First part SVGD_PHI_SPLIT_FRAC percent of the rows, default 50
+    // (cfg3 8-rank share, profiles/r04_sim_world.jsonl: 50 % 0.632 ms,
+    // 62 % 0.783, 72 % 0.765 -- uneven parts made phi itself 40 % slower)
+    c->split_h = (c->nrows * c->knobs.phi_split_frac.or_(50) / 100) / rows_wg * rows_wg;
+    if (c->split_h >= c->nrows) c->split_h = 0;
+    if (c->split_h > 0) {
+        c->S2 = splits(c->split_h);
+        c->S2b = splits(c->nrows - c->split_h);
+    }
+    CHK(dalloc(c, &c->rec, c->np * c->RS));
+    CHK(dalloc(c, &c->xf, c->np * med_f32_stride(dim)));
+    CHK(dalloc(c, &c->nmax, 2)); // one slot per X version parity (center)
+    CHK(dalloc(c, &c->part, std::max({(int64_t)c->S * c->ldp, (int64_t)c->S2 * c->split_h,
+                                      (int64_t)c->S2b * (c->nrows - c->split_h)}) * (dim + 1)));
+    if (p.path == PHI_SYM) CHK(setup_sym(c, ncu));
+    // the centring fold (svgd_ctx::cpart)
+    c->cpart_stride = (int64_t)center_fold_grid(dim, c->np) * dim;
+    CHK(dalloc(c, &c->cpart, 2 * c->cpart_stride));
+    return SVGD_OK;
+}
+
+// Step 3: the particles, their centred copies and the planned phi path's operands.
+int alloc_phi(svgd_ctx *c)
+{
+    const PhiPlan &p = c->plan;
+    const int dim = c->dim;
     const int64_t rows_all = c->chunk * c->world;
     CHK(dalloc(c, &c->X, rows_all * dim));
     CHK(dalloc(c, &c->G, rows_all * dim));
-    CHK(dalloc(c, &c->xc, c->np * c->KP));
+    CHK(dalloc(c, &c->xc, c->np * p.KP));
     CHK(dalloc(c, &c->nrm, c->np));
     CHK(dalloc(c, &c->cvec, c->np));
-    c->rowpath = dim <= ROWS_MAX_D && !f32;
-    if (f32) {
-        CHK(dalloc(c, &c->xcf, c->np * c->KP));
+    if (c->dtype == SVGD_F32) {
+        CHK(dalloc(c, &c->xcf, c->np * p.KP));
         CHK(dalloc(c, &c->nrmf, c->np));
         CHK(dalloc(c, &c->cvf, c->np));
         // KP 32 / 64: the median keys on the bf16 matrix cores (their parts)
-        if (const int64_t w = median_key_part_words(c->KP, c->np)) CHK(dalloc(c, &c->XK, w));
+        if (const int64_t w = median_key_part_words(p.KP, c->np)) CHK(dalloc(c, &c->XK, w));
     }
-    if (c->rowpath) {
-        // column splits: enough workgroups to fill every CU at the kernel's occupancy
-        int ncu = 256;
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, device) == hipSuccess) ncu = prop.multiProcessorCount;
-        c->R = dim <= 8 ? 4 : 2; // rows per lane (register budget)
-        // 8-wave work-groups, 8192-entry table, columns split over the waves
-        // (kind 2); the 4-wave kernel (kind 0) serves the full-matrix scales
-        // (signature rows) and an R the 8-wave build does not have
-        if (phi_rows_t8k_supported(dim, c->R)) c->phi_kind = 2;
-        const int64_t resident = (int64_t)phi_rows_blocks_per_cu(dim, c->R, c->phi_kind) * ncu;
-        const int64_t rows_wg = c->phi_kind == 2 ? phi_rows_t8k_rows(c->R) : 256 * (int64_t)c->R;
-        const int64_t iblocks = std::max<int64_t>(1, (c->nrows + rows_wg - 1) / rows_wg);
-        int64_t S = std::max<int64_t>(1, (resident + iblocks - 1) / iblocks);
-        // 2 blocks per resident slot: one block wave per slot left a tail of
-        // idle CUs (measured at cfg3, phi launch: S x1 4.00 ms, x2 3.83-3.93,
-        // x4 3.81-3.90, x8 3.91-3.95 -- x2 and x4 tie, x2 has half the partials)
-        constexpr int split_mult = 2;
-        S *= split_mult;
-        S = std::min<int64_t>(S, std::max<int64_t>(1, n / 256));
-        c->S = (int)S;
-        c->RS = phi_rec_stride(dim);
-        c->ldp = std::max<int64_t>(1, c->nrows);
-        // two row parts (svgd_step_host_model at P > 1, split_rows policy
-        // below): the first part's rows get their X_{t+1} while the second
-        // part's phi still runs; the second part's gradient has to fit in the
-        // next step's median phase.  Each launch takes its own column splits.
-        // First part SVGD_PHI_SPLIT_FRAC percent of the rows, default 50
-        // (cfg3 8-rank share, profiles/r04_sim_world.jsonl: 50 % 0.632 ms,
-        // 62 % 0.783, 72 % 0.765 -- uneven parts made phi itself 40 % slower)
-        int frac = 50;
-        if (const char *e = std::getenv("SVGD_PHI_SPLIT_FRAC")) frac = std::min(90, std::max(10, std::atoi(e)));
-        c->split_h = (c->nrows * frac / 100) / rows_wg * rows_wg;
-        if (c->split_h >= c->nrows) c->split_h = 0;
-        auto splits = [&](int64_t rows) {
-            const int64_t ib = std::max<int64_t>(1, (rows + rows_wg - 1) / rows_wg);
-            const int64_t s = std::max<int64_t>(1, (resident + ib - 1) / ib) * split_mult;
-            return (int)std::min<int64_t>(s, std::max<int64_t>(1, n / 256));
-        };
-        if (c->split_h > 0) {
-            c->S2 = splits(c->split_h);
-            c->S2b = splits(c->nrows - c->split_h);
-        }
-        CHK(dalloc(c, &c->rec, c->np * c->RS));
-        CHK(dalloc(c, &c->xf, c->np * med_f32_stride(dim)));
-        CHK(dalloc(c, &c->nmax, 2)); // one slot per X version parity (center)
-        CHK(dalloc(c, &c->part, std::max({(int64_t)c->S * c->ldp, (int64_t)c->S2 * c->split_h,
-                                          (int64_t)c->S2b * (c->nrows - c->split_h)}) * (dim + 1)));
-        // symmetric phi pass: isotropic scales, d <= 8 (a pair feeds two
-        // particles).  One rank: default since round 5 from N = 32768 up (with 16-byte record reads
-        // cfg3 phi 3.59 -> 3.08 ms, step 4.12 -> 3.68 ms, cfg4 65.5 -> 56.5
-        // ms; at cfg2, N = 16384, its extra launches outweigh the saving,
-        // 0.200 vs 0.265 ms -- profiles/r05_sym_ab.txt.  SVGD_PHI_SYM=1 / 0
-        // forces it on / off)
-        // P > 1: rank r runs the units [U r / P, U (r+1) / P), sums every
-        // particle's partials from them and a point-to-point exchange hands
-        // each rank the pieces of its rows (sym_exchange).  Its phi saving
-        // grows as N^2 / P, the exchange as N.  Round 5 (a reduce-scatter of
-        // all N (d+1) sums, units not balanced at P = 8): default from N / P >=
-        // 16384 (cfg3 shares P = 2 2.008 -> 1.875 ms, P = 4 1.066 -> 1.003, P =
-        // 8 0.587 -> 0.582; cfg4 P = 8 7.92 -> 6.84 ms, profiles/r05_sim_sym.txt,
-        // r05_cfg4_sim8_sym.txt).  Round 6: the padding-only sub-tiles left out
-        // of the units (11 per work-group at cfg3 P = 8 instead of 11 or 12) and
-        // ~2.5 MB sent per rank at cfg3 P = 8 instead of 4.1 MB in ring steps:
-        // default from N / P >= 8192 (cfg3 at P = 8 included)
-        bool want_sym = phi_sym_supported(dim) && n >= 32768 && n / c->plan_world >= 8192;
-        int sym_env = -1; // 2 (a test knob): the P > 1 form (sums, reduce-scatter, apply) at any P
-        if (const char *e = std::getenv("SVGD_PHI_SYM")) {
-            sym_env = std::atoi(e);
-            want_sym = phi_sym_supported(dim) && sym_env != 0;
-        }
-        if (want_sym && phi_sym_geom(dim, &c->symB, &c->symSRS, &c->symNSUB)) {
-            const int64_t B = c->symB;
-            c->sym_nb = (n + B - 1) / B;
-            c->sym_units = svgd_plan_sym_total(n, (int)B, c->symNSUB); // (no padding-only sub-tiles)
-            const int64_t Pw = c->plan_world, r = c->sim_world > 1 ? 0 : c->rank;
-            const int64_t slots = (int64_t)phi_sym_blocks_per_cu(dim) * ncu;
-            const int64_t Vr = c->sym_units * (r + 1) / Pw - c->sym_units * r / Pw;
-            c->sym_grid = (int)std::max<int64_t>(1, std::min<int64_t>(Vr, slots));
-            // the rank's units, the row blocks each work-group's contiguous run
-            // visits and each row block's contiguous row-sum records (plan.cpp)
-            const int64_t nbs = c->sym_nb;
-            std::vector<int> tab(3 * (size_t)nbs + 2 * (size_t)c->sym_grid);
-            int *blkg = tab.data(), *rbase = blkg + 2 * nbs, *wst = rbase + nbs;
-            const int64_t nrec = svgd_plan_sym_units(n, (int)B, c->symNSUB, (int)Pw, (int)r, c->sym_grid,
-                                                     &c->sym_u0, &c->sym_u1, blkg, rbase, &c->sym_Ia, &c->sym_Ib);
-            // each work-group's first unit (the kernel advances from there)
-            for (int g = 0; g < c->sym_grid; ++g) {
-                const int64_t V = c->sym_u1 - c->sym_u0;
-                int64_t t = 0, q = 0;
-                svgd_plan_sym_unit(n, (int)B, c->symNSUB, c->sym_u0 + V * g / c->sym_grid, &t, &q);
-                wst[2 * g] = (int)t;
-                wst[2 * g + 1] = (int)q;
-            }
-            {
-                const int64_t sub = B / c->symNSUB, valid = n - (nbs - 1) * B;
-                c->sym_qlast = (int)((valid + sub - 1) / sub);
-            }
-            c->sym_SM = (nbs - 1) / 2 + 2;
-            // the row stream's hand-over inside k_phi_sym (symok = 0): its
-            // 8-wave work-groups, one wave of them (<= c->S, the part buffer's splits)
-            {
-                const int64_t rows_wg = phi_rows_t8k_rows(4);
-                const int64_t ib = std::max<int64_t>(1, (c->nrows + rows_wg - 1) / rows_wg);
-                c->sym_fS = (int)std::max<int64_t>(1, std::min<int64_t>(c->S, ncu / ib));
-            }
-            CHK(dalloc(c, &c->sym_tab, (int64_t)tab.size()));
-            HIPCHK(c, hipMemcpyAsync(c->sym_tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice,
-                                     c->stream)); // (after dalloc's memset on the same stream)
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            CHK(dalloc(c, &c->srec, c->sym_nb * B * c->symSRS));
-            CHK(dalloc(c, &c->rowpart, nrec * B * (dim + 1)));
-            // zeroed here once: entries no unit of this rank writes stay zero
-            CHK(dalloc(c, &c->colpart, nbs * c->sym_SM * B * (dim + 1)));
-            CHK(dalloc(c, &c->symok, 1));
-            CHK(dalloc(c, &c->tab8k, 8192));
-            HIPCHK(c, launch_fill_tab8k(c->tab8k, c->stream));
-            if (Pw > 1 || sym_env == 2) CHK(dalloc(c, &c->contrib, std::max<int64_t>(c->np, c->world * c->chunk) * (dim + 1)));
-            if (c->world > 1) {
-                // the exchange plan: the same ranges on both sides of every pair of ranks
-                c->xsend.assign(2 * (size_t)c->world, 0);
-                c->xrecv.assign(3 * (size_t)c->world, 0);
-                for (int q = 0; q < c->world; ++q) {
-                    int64_t a, b;
-                    svgd_plan_sym_exchange(n, (int)B, c->symNSUB, c->world, c->rank, q, &a, &b);
-                    c->xsend[2 * q] = a;
-                    c->xsend[2 * q + 1] = q == c->rank ? a : b; // (its own rows: not sent)
-                    svgd_plan_sym_exchange(n, (int)B, c->symNSUB, c->world, q, c->rank, &a, &b);
-                    if (q != c->rank && b > a) {
-                        c->xrecv[3 * q] = a;
-                        c->xrecv[3 * q + 1] = b;
-                        c->xrecv[3 * q + 2] = c->xrecv_rows;
-                        c->xrecv_rows += b - a;
-                    }
-                }
-                CHK(dalloc(c, &c->xrecv_buf, std::max<int64_t>(1, c->xrecv_rows) * (dim + 1)));
-                HIPCHK(c, hipMalloc((void **)&c->xtab_d, c->xrecv.size() * sizeof(int64_t)));
-                HIPCHK(c, hipMemcpy(c->xtab_d, c->xrecv.data(), c->xrecv.size() * sizeof(int64_t),
-                                    hipMemcpyHostToDevice));
-            }
-            c->sym = true;
-        }
-        // the centring fold (svgd_ctx::cpart)
-        c->cpart_stride = (int64_t)center_fold_grid(dim, c->np) * dim;
-        CHK(dalloc(c, &c->cpart, 2 * c->cpart_stride));
-    } else {
-        CHK(dalloc(c, &c->V, c->np * c->VW));
-        if (f32) CHK(dalloc(c, &c->Vf, c->np * c->VW));
-        if (f32 && phi_f32s_supported(c->KP, c->NCB) && !std::getenv("SVGD_PHI_TILE_GENERIC")) {
-            // np is a multiple of 2 TBJ_COLS: ceil(n / TBJ_COLS) tiles fit
-            if (c->want_b3) {
-                CHK(dalloc(c, &c->B3, (c->np / TBJ_COLS) * phi_b3_tile_words(c->KP, c->NCB)));
-            } else {
-                CHK(dalloc(c, &c->XS, c->np * c->KP));
-                CHK(dalloc(c, &c->VS, c->np * 16 * (c->NCB + 1)));
-            }
-        }
+    if (!p.rows()) CHK(dalloc(c, &c->V, c->np * p.VW));
+    switch (p.path) {
+    case PHI_SYM:
+    case PHI_ROWS:
+        CHK(alloc_phi_rows(c));
+        break;
+    case PHI_B3: // np is a multiple of 2 TBJ_COLS: ceil(n / TBJ_COLS) tiles fit
+        CHK(dalloc(c, &c->B3, (c->np / TBJ_COLS) * phi_b3_tile_words(p.KP, p.NCB)));
+        break;
+    case PHI_F32S:
+        CHK(dalloc(c, &c->XS, c->np * p.KP));
+        CHK(dalloc(c, &c->VS, c->np * 16 * (p.NCB + 1)));
+        break;
+    case PHI_TILE_F32: // the row-major fp32 copy of V
+        CHK(dalloc(c, &c->Vf, c->np * p.VW));
+        break;
+    case PHI_TILE_F64:
+        break;
     }
     CHK(dalloc(c, &c->phi, std::max<int64_t>(1, c->nrows) * dim));
     CHK(dalloc(c, &c->m, std::max<int64_t>(1, c->nrows) * dim));
@@ -2086,30 +2089,51 @@ int init_ctx(svgd_ctx *c, int dim, int64_t n, int dtype, int device, int sim_wor
     CHK(dalloc(c, &c->upper, dim));
     CHK(dalloc(c, &c->partial, (int64_t)c->nparts * dim));
     CHK(dalloc(c, &c->scal, 2));
+    return SVGD_OK;
+}
+
+// Step 4: the median's buffers and its knobs.
+int alloc_median(svgd_ctx *c)
+{
+    const Knobs &k = c->knobs;
     CHK(dalloc(c, &c->counts, 4 * MAX_COLLECT_BLOCKS)); // <= 4 regions per collect block
     CHK(dalloc(c, &c->below, 4 * MAX_COLLECT_BLOCKS));
     CHK(dalloc(c, &c->cnt3, CNT_LEN + 3));
     CHK(dalloc(c, &c->bpart, (int64_t)MAX_COLLECT_BLOCKS * NBK));
     CHK(dalloc(c, &c->gseg, (int64_t)c->world * (CAPG + 1)));
-    if (const char *e = std::getenv("SVGD_BUCKET_CAP")) c->bucket_cap = std::atoll(e);
-    if (const char *e = std::getenv("SVGD_MEDIAN_SAMPLE")) c->sample_size = std::max<int64_t>(1, std::atoll(e));
-    // A/B and test knob: the reference collect passes (k_pair_rows / k_pair_tiles
-    // MODE 0) instead of the matrix-core ones (k_pair_mcol / k_pair_tcol)
-    if (const char *e = std::getenv("SVGD_COLLECT_FP64")) c->mcol = std::atoi(e) == 0;
-    if (const char *e = std::getenv("SVGD_MCOL_BF16")) c->mcol_bf16 = std::atoi(e) != 0;
-    if (c->xf && c->mcol && c->mcol_bf16 && dim <= 8) { // the collect's split-bf16 operands (center)
+    c->bucket_cap = k.bucket_cap.or_(c->bucket_cap);
+    c->sample_size = k.median_sample.or_(c->sample_size);
+    c->bracket_sigma = k.median_sigma.or_(c->bracket_sigma);
+    // A/B and test knob (SVGD_COLLECT_FP64=1): the reference collect passes
+    // (k_pair_rows / k_pair_tiles MODE 0) instead of the matrix-core ones
+    // (k_pair_mcol / k_pair_tcol)
+    c->mcol = k.mcol.or_(c->mcol);
+    // k_pair_mcol's Gram as split bf16 (d <= 8; SVGD_MCOL_BF16=0: f32): its operands (center)
+    if (c->xf && c->mcol && k.mcol_bf16.or_(1) && c->dim <= 8) {
         CHK(dalloc(c, &c->xsplit, c->np * 8));
         c->collect_blocks = 1280; // k_pair_mcol<D, true>: 5 work-groups per CU (31 KiB LDS, <= 96 VGPRs)
     }
-    if (const char *e = std::getenv("SVGD_MEDIAN_SIGMA")) c->bracket_sigma = std::max(0.0, std::atof(e));
     CHK(dalloc(c, &c->st, 1));
     CHK(dalloc(c, &c->ghist, 2 * RADIX));
     CHK(dalloc(c, &c->ccount, 1));
-    const size_t hb = sizeof(double) * (size_t)std::max<int64_t>(1, c->nrows) * dim;
+    CHK(dalloc(c, &c->d_status, 1));
+    c->trk_allowed = k.track_bracket.or_(c->trk_allowed);
+    // A miss redoes the step; the band it saves is collect-pass work, which
+    // outweighs the misses' cost only when the collect is large: 2.5 x the
+    // recent error from N = 32768 up (cfg3: median phase 0.550 -> 0.513 ms,
+    // 86 instead of 72 of 90 steps tracked, no miss in 360), 4 below (cfg2
+    // at 2.5: 3 misses in 180 steps, slower) -- profiles/r04_track_mult_ab.txt
+    c->trk_err_mult = k.track_err_mult.or_(c->n >= 32768 ? 2.5 : 4.0);
+    return SVGD_OK;
+}
+
+// Step 5: pinned host memory and the events.
+int alloc_host(svgd_ctx *c)
+{
+    const size_t hb = sizeof(double) * (size_t)std::max<int64_t>(1, c->nrows) * c->dim;
     HIPCHK(c, hipHostMalloc((void **)&c->h_x, hb, hipHostMallocDefault));
     HIPCHK(c, hipHostMalloc((void **)&c->h_g, hb, hipHostMallocDefault));
-    c->xmirror = hb <= XMIRROR_MAX;
-    if (const char *e = std::getenv("SVGD_X_MIRROR")) c->xmirror = std::atoi(e) != 0;
+    c->xmirror = c->knobs.x_mirror.or_(hb <= XMIRROR_MAX);
     if (c->xmirror) {
         // coherent: the update epilogue writes it uncached (the host reads it
         // once the step's end event has passed); only a mirroring context pins it
@@ -2119,31 +2143,22 @@ int init_ctx(svgd_ctx *c, int dim, int64_t n, int dtype, int device, int sim_wor
     HIPCHK(c, hipHostMalloc((void **)&c->h_cnt, (CNT_LEN + 3) * sizeof(unsigned long long),
                             hipHostMallocDefault));
     HIPCHK(c, hipHostMalloc((void **)&c->h_scal, 2 * sizeof(double), hipHostMallocDefault));
-    HIPCHK(c, hipEventCreateWithFlags(&c->ev_x, hipEventDisableTiming));
-    HIPCHK(c, hipEventCreateWithFlags(&c->ev_xready, hipEventDisableTiming));
-    HIPCHK(c, hipEventCreateWithFlags(&c->ev_g, hipEventDisableTiming));
+    for (hipEvent_t *e : {&c->ev_x, &c->ev_xready, &c->ev_g, &c->ev_cnt, &c->ev_scal, &c->ev_fin,
+                          &c->ev_status, &c->ev_xhalf})
+        HIPCHK(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
     for (auto &e : c->ev_xch) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    HIPCHK(c, hipEventCreateWithFlags(&c->ev_cnt, hipEventDisableTiming));
-    HIPCHK(c, hipEventCreateWithFlags(&c->ev_scal, hipEventDisableTiming));
-    HIPCHK(c, hipEventCreateWithFlags(&c->ev_fin, hipEventDisableTiming));
-    HIPCHK(c, hipEventCreateWithFlags(&c->ev_status, hipEventDisableTiming));
-    CHK(dalloc(c, &c->d_status, 1));
     HIPCHK(c, hipHostMalloc((void **)&c->h_status, sizeof(int), hipHostMallocCoherent));
     *c->h_status = 0;
     HIPCHK(c, hipHostGetDevicePointer((void **)&c->h_status_dev, c->h_status, 0));
     HIPCHK(c, hipHostMalloc((void **)&c->h_trk, 16 * sizeof(uint64_t), hipHostMallocCoherent));
     std::memset(c->h_trk, 0, 16 * sizeof(uint64_t));
     HIPCHK(c, hipHostGetDevicePointer((void **)&c->h_trk_dev, c->h_trk, 0));
-    if (const char *e = std::getenv("SVGD_SPECULATE")) c->spec_allowed = std::atoi(e) != 0;
-    if (const char *e = std::getenv("SVGD_TRACK_BRACKET")) c->trk_allowed = std::atoi(e) != 0;
-    if (const char *e = std::getenv("SVGD_TRACK_MIN_WIDTH")) c->trk_min_w = std::atof(e);
-    // A miss redoes the step; the band it saves is collect-pass work, which
-    // outweighs the misses' cost only when the collect is large: 2.5 x the
-    // recent error from N = 32768 up (cfg3: median phase 0.550 -> 0.513 ms,
-    // 86 instead of 72 of 90 steps tracked, no miss in 360), 4 below (cfg2
-    // at 2.5: 3 misses in 180 steps, slower) -- profiles/r04_track_mult_ab.txt
-    c->trk_err_mult = n >= 32768 ? 2.5 : 4.0;
-    if (const char *e = std::getenv("SVGD_TRACK_ERR_MULT")) c->trk_err_mult = std::atof(e);
+    return SVGD_OK;
+}
+
+// Step 6: the host gradient's threads and whether phi runs in two row parts.
+void host_policy(svgd_ctx *c)
+{
     // half the OpenMP threads, but no more than this rank's share of the
     // cgroup CPU quota (ranks of one node share it; OpenMP sees the affinity
     // mask, not the quota) and at most 32 (the gradient of a 65536-row share
@@ -2153,16 +2168,11 @@ int init_ctx(svgd_ctx *c, int dim, int64_t n, int dtype, int device, int sim_wor
     // share of the node's quota is this one-GPU box's whole quota
     // (SVGD_HOST_THREADS=2 reproduces the 16-CPU box split 8 ways, the
     // pessimistic bound of rounds 3-5).
-    {
-        int t = std::max(1, omp_get_max_threads() / 2);
-        const int q = cgroup_cpus();
-        c->cpu_quota = q;
-        const int sharing = c->sim_world > 1 ? 1 : std::max(1, c->plan_world);
-        if (q > 0) t = std::min(t, std::max(1, q / sharing));
-        c->host_threads = std::min(t, 32);
-    }
-    if (const char *e = std::getenv("SVGD_HOST_THREADS")) c->host_threads = std::max(1, std::atoi(e));
-    if (const char *e = std::getenv("SVGD_DEBUG_COLL")) c->dbg_coll = std::atoi(e) != 0;
+    int t = std::max(1, omp_get_max_threads() / 2);
+    c->cpu_quota = cgroup_cpus();
+    const int sharing = c->sim_world > 1 ? 1 : std::max(1, c->plan_world);
+    if (c->cpu_quota > 0) t = std::min(t, std::max(1, c->cpu_quota / sharing));
+    c->host_threads = c->knobs.host_threads.or_(std::min(t, 32));
     // phi in row halves when a rank of 4 or more has more rows per gradient
     // thread than the device's median phase hides: then phi waited for G;
     // with halves the first half's gradient runs beside the second half's
@@ -2172,14 +2182,35 @@ int init_ctx(svgd_ctx *c, int dim, int64_t n, int dtype, int device, int sim_wor
     // 0.714 -> 0.656 ms).  AVX-512 block (~7 us per 1000 rows and thread on
     // the EPYC 9575F): the whole-rows step wins at P = 8 and 4
     // (profiles/r05_sim_split_ab.txt: 0.580 vs 0.598 ms, 1.052 vs 1.077 ms),
-    // split above 8192 rows per thread.
-    {
-        const int64_t per_thread = svgd_amd::host_grad_avx512() ? 8192 : 2048;
-        c->split_rows = c->rowpath && c->split_h > 0 && c->plan_world >= 4 &&
-                        c->nrows > per_thread * (int64_t)std::max(1, c->host_threads);
-    }
-    if (const char *e = std::getenv("SVGD_PHI_SPLIT")) c->split_rows = c->rowpath && c->split_h > 0 && std::atoi(e) != 0;
-    HIPCHK(c, hipEventCreateWithFlags(&c->ev_xhalf, hipEventDisableTiming));
+    // split above 8192 rows per thread.  SVGD_PHI_SPLIT replaces the policy,
+    // not the need for a row stream with a first part.
+    const int64_t per_thread = svgd_amd::host_grad_avx512() ? 8192 : 2048;
+    const bool policy = c->plan_world >= 4 && c->nrows > per_thread * (int64_t)std::max(1, c->host_threads);
+    c->split_rows = c->rowpath && c->split_h > 0 && c->knobs.phi_split.or_(policy);
+}
+
+// A context's creation, after its knobs, world and rank are set.
+int init_ctx(svgd_ctx *c, int dim, int64_t n, int dtype, int device, int sim_world = 1)
+{
+    if (dim <= 0 || n <= 0)
+        return fail(c, SVGD_ERR_DIM, "[Dimension Error] Particle count and dimension must be positive.");
+    if (dtype != SVGD_F64 && dtype != SVGD_F32)
+        return fail(c, SVGD_ERR_ARG, "[Argument Error] dtype must be SVGD_F64 or SVGD_F32.");
+    c->dim = dim;
+    c->n = n;
+    c->dtype = dtype;
+    c->device = device;
+    plan_rows_tiles(c, sim_world);
+    if (!plan_phi(dim, n, dtype, c->plan_world, c->row0, c->knobs, phi_caps(dim, dtype), &c->plan))
+        return fail(c, SVGD_ERR_DIM, "[Dimension Error] Device path supports dimension <= 64.");
+    c->rowpath = c->plan.rows();
+    HIPCHK(c, hipSetDevice(device));
+    HIPCHK(c, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    HIPCHK(c, hipStreamCreateWithFlags(&c->cstream, hipStreamNonBlocking));
+    CHK(alloc_phi(c));
+    CHK(alloc_median(c));
+    CHK(alloc_host(c));
+    host_policy(c);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return SVGD_OK;
 }
@@ -2199,10 +2230,7 @@ int svgd_get_unique_id(void *unique_id128)
 
 int svgd_create(svgd_ctx **out, int dim, int64_t n, int dtype, int device)
 {
-    if (!out) return SVGD_ERR_ARG;
-    svgd_ctx *c = new svgd_ctx();
-    *out = c;
-    return init_ctx(c, dim, n, dtype, device);
+    return svgd_create_sim(out, dim, n, dtype, device, 1); // (a world of one: nothing simulated)
 }
 
 int svgd_create_sim(svgd_ctx **out, int dim, int64_t n, int dtype, int device, int sim_world)
@@ -2210,6 +2238,7 @@ int svgd_create_sim(svgd_ctx **out, int dim, int64_t n, int dtype, int device, i
     if (!out) return SVGD_ERR_ARG;
     svgd_ctx *c = new svgd_ctx();
     *out = c;
+    c->knobs = read_knobs();
     if (sim_world < 1) return fail(c, SVGD_ERR_ARG, "[Argument Error] Invalid simulated world size.");
     return init_ctx(c, dim, n, dtype, device, sim_world);
 }
@@ -2220,13 +2249,14 @@ int svgd_create_dist(svgd_ctx **out, int dim, int64_t n, int dtype, int device, 
     if (!out) return SVGD_ERR_ARG;
     svgd_ctx *c = new svgd_ctx();
     *out = c;
-    if (world < 1 || rank < 0 || rank >= world ||
-        (world > 1 && !unique_id128 && !std::getenv("SVGD_HOSTCOMM")))
+    c->knobs = read_knobs();
+    const Knobs &k = c->knobs;
+    if (world < 1 || rank < 0 || rank >= world || (world > 1 && !unique_id128 && !k.hostcomm.set))
         return fail(c, SVGD_ERR_ARG, "[Argument Error] Invalid world/rank.");
     c->world = world;
     c->rank = rank;
     CHK(init_ctx(c, dim, n, dtype, device));
-    if (world > 1 && std::getenv("SVGD_HOSTCOMM")) {
+    if (world > 1 && k.hostcomm.set) {
         // rehearsal backend: ranks sharing one GPU, collectives through host shm
         const size_t slot = std::max<size_t>(
             std::max<size_t>(
@@ -2236,7 +2266,7 @@ int svgd_create_dist(svgd_ctx **out, int dim, int64_t n, int dtype, int device, 
         const size_t slot_rs = c->contrib ? 2 * sizeof(int64_t) * (size_t)world +
                                                 (size_t)c->n * (c->dim + 1) * sizeof(double)
                                           : 0;
-        if (hostcomm_create(&c->hcomm, std::getenv("SVGD_HOSTCOMM"), world, rank, std::max(slot, slot_rs)))
+        if (hostcomm_create(&c->hcomm, k.hostcomm.v.c_str(), world, rank, std::max(slot, slot_rs)))
             return fail(c, SVGD_ERR_RCCL, "[RCCL Error] host communicator setup failed.");
         return SVGD_OK;
     }
@@ -2254,9 +2284,7 @@ int svgd_create_dist(svgd_ctx **out, int dim, int64_t n, int dtype, int device, 
         // over comm): one rank gathering G on gcomm while another gathers it
         // on comm would hang both, so any failure drops gcomm everywhere and
         // the G all-gather stays on the compute stream.
-        bool want_g = world > 1;
-        if (const char *e = std::getenv("SVGD_G_COMM")) want_g = std::atoi(e) != 0;
-        if (want_g) {
+        if (k.g_comm.or_(world > 1)) {
             int ok = ncclCommSplit(c->comm, 0, rank, &c->gcomm, nullptr) == ncclSuccess && c->gcomm;
             if (ok && hipStreamCreateWithFlags(&c->gstream, hipStreamNonBlocking) != hipSuccess) ok = 0;
             if (ok && hipEventCreateWithFlags(&c->ev_gg, hipEventDisableTiming) != hipSuccess) ok = 0;
@@ -2403,8 +2431,8 @@ int alloc_matrix_scale(svgd_ctx *c)
     CHK(dalloc(c, &c->sc_sgn, c->dim));
     CHK(dalloc(c, &c->sc_work, 2 * dd));
     CHK(dalloc(c, &c->wv, c->np * c->dim));
-    if (!c->rowpath) CHK(dalloc(c, &c->zc, c->np * c->KP));
-    if (c->dtype == SVGD_F32) CHK(dalloc(c, &c->zcf, c->np * c->KP));
+    if (!c->rowpath) CHK(dalloc(c, &c->zc, c->np * c->plan.KP));
+    if (c->dtype == SVGD_F32) CHK(dalloc(c, &c->zcf, c->np * c->plan.KP));
     CHK(dalloc(c, &c->sc_err, 1));
     HIPCHK(c, hipHostMalloc((void **)&c->h_err, sizeof(int), hipHostMallocDefault));
     *c->h_err = 0;
@@ -3042,31 +3070,27 @@ int svgd_get_timing(svgd_ctx *c, double *phi_ms, double *median_ms, int64_t *cou
     return SVGD_OK;
 }
 
+// (The plan is made at creation and a matrix scale is chosen afterwards, so
+// the name stays the isotropic-scale kernel's: under a matrix scale a row
+// stream or symmetric-pass context launches k_phi_rows<D, R, 4, 4096, 1>.)
 int svgd_phi_kernel_name(const svgd_ctx *c, char *buf, int cap)
 {
     if (!c || !buf || cap <= 0) return SVGD_ERR_ARG;
-    char s[96];
-    const int d = c->dim;
-    if (c->rowpath && c->sym) {
-        std::snprintf(s, sizeof s, "k_phi_sym<%d>", d);
-    } else if (c->rowpath) {
-        if (c->phi_kind == 2)
-            std::snprintf(s, sizeof s, "k_phi_rows<%d, %d, 8, 8192, 8>", d, c->R);
-        else
-            std::snprintf(s, sizeof s, "k_phi_rows<%d, %d, 4, 4096, 1>", d, c->R);
-    } else if (c->dtype == SVGD_F32 && c->B3) {
-        std::snprintf(s, sizeof s, "k_phi_b3<%d, %d, 8, %s, %d>", c->KP, c->NCB,
-                      16 * c->NCB == d ? "true" : "false", c->b3_rg);
-    } else if (c->dtype == SVGD_F32 && c->XS) {
-        std::snprintf(s, sizeof s, "k_phi_f32s<%d, %d>", c->KP, c->NCB);
-    } else {
-        const bool f64 = c->dtype != SVGD_F32;
-        int nw = 4, pre = 0;
-        phi_tile_cfg(f64, &nw, &pre);
-        std::snprintf(s, sizeof s, "k_phi<%s, %d, %d, %d, %s, %s>", f64 ? "double" : "float", c->KP,
-                      c->NCB, nw, pre ? "true" : "false", c->dim == 16 * c->NCB ? "true" : "false");
-    }
-    std::snprintf(buf, (size_t)cap, "%s", s);
+    phi_plan_name(c->plan, phi_caps(c->dim, c->dtype), buf, cap);
+    return SVGD_OK;
+}
+
+int svgd_plan_phi_name(int dim, int64_t n, int dtype, int world, int rank, char *buf, int cap)
+{
+    if (!buf || cap <= 0 || n <= 0 || world < 1 || rank < 0 || rank >= world ||
+        (dtype != SVGD_F64 && dtype != SVGD_F32))
+        return SVGD_ERR_ARG;
+    int64_t row0 = 0, row1 = 0;
+    svgd_plan_rows(n, world, rank, &row0, &row1);
+    PhiPlan p;
+    const PhiCaps caps = phi_caps(dim, dtype);
+    if (!plan_phi(dim, n, dtype, world, row0, read_knobs(), caps, &p)) return SVGD_ERR_DIM;
+    phi_plan_name(p, caps, buf, cap);
     return SVGD_OK;
 }
 

@@ -1,5 +1,5 @@
 // Host-code sanitizer driver (AddressSanitizer + UndefinedBehaviorSanitizer):
-// the planner (plan.cpp), the host Gaussian-sum models (host_models.cpp) and
+// the planner (plan.cpp, the phi plan included), the host Gaussian-sum models (host_models.cpp) and
 // the CPU oracle (oracle/svgd_oracle.c, test infrastructure) built with
 // -fsanitize=address,undefined and exercised with cross-checks
 // (`make sanitize`, run by tests/test_sanitize.py).  The HIP-side host code
@@ -9,9 +9,11 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "../../include/svgdcpp_amd/svgd_capi.h"
+#include "../../svgdcpp_amd/csrc/plan.h"
 
 extern "C" {
 void or_fill_splitmix(double *X, long count, double scale, uint64_t seed);
@@ -105,6 +107,83 @@ static void test_plan()
     CHECK(svgd_plan_bucket_select(cnt.data(), 2048, 2, bad, bsel, rin, &tot) == -1);
 }
 
+// plan_phi over every dimension, both dtypes, three world sizes and the A/B
+// knobs, with the capability flags as the launchers answer them today
+// (svgd_kernels.hip: phi_*_supported, phi_tile_s1v, med_rec_stride).
+static void test_phi_plan()
+{
+    using namespace svgd_amd;
+    std::vector<Knobs> settings(8);
+    settings[1].phi_tile_generic = true;
+    settings[2].phi_b3 = {true, 0};
+    settings[3].phi_s1v = {true, 0};
+    settings[4].phi_b3_rg = {true, 2};
+    settings[5].phi_sym = {true, 0};
+    settings[6].phi_sym = {true, 1};
+    settings[7].phi_sym = {true, 2};
+    PhiPlan p;
+    char name[96];
+    PhiCaps c8{};
+    c8.rows_kp = 12, c8.rows_t8k = c8.sym = true;
+    CHECK(plan_phi(8, 65536, SVGD_F64, 1, 0, settings[0], c8, &p));
+    phi_plan_name(p, c8, name, (int)sizeof name);
+    CHECK(std::strcmp(name, "k_phi_sym<8>") == 0);
+    CHECK(plan_phi(8, 333, SVGD_F64, 1, 0, settings[0], c8, &p));
+    phi_plan_name(p, c8, name, (int)sizeof name);
+    CHECK(std::strcmp(name, "k_phi_rows<8, 4, 8, 8192, 8>") == 0);
+    CHECK(!plan_phi(65, 333, SVGD_F64, 1, 0, settings[0], PhiCaps{}, &p));
+    CHECK(!plan_phi(0, 333, SVGD_F64, 1, 0, settings[0], PhiCaps{}, &p));
+    for (int d = 1; d <= 64; ++d) {
+        int KP = 0, NCB = 0;
+        CHECK(pick_tiles(d, &KP, &NCB));
+        PhiCaps cap{};
+        cap.rows_kp = d <= 16 ? ((d + 1 + 3) / 4) * 4 : 0;
+        cap.rows_t8k = d <= 16;
+        cap.sym = d <= 8;
+        cap.tile_s1v = d > 16 && d % 16 == 0;
+        cap.f32s = KP % 16 == 0;
+        cap.b3 = KP == 32 || KP == 64;
+        cap.b3_waves = 8;
+        for (int dtype : {SVGD_F64, SVGD_F32})
+            for (int world : {1, 2, 8})
+                for (int64_t n : {int64_t(333), int64_t(65536)})
+                    for (int rank = 0; rank < world; ++rank)
+                        for (const Knobs &k : settings) {
+                            int64_t r0, r1;
+                            svgd_plan_rows(n, world, rank, &r0, &r1);
+                            CHECK(plan_phi(d, n, dtype, world, r0, k, cap, &p));
+                            const bool f32 = dtype == SVGD_F32;
+                            cap.tile_waves = f32 ? 4 : 8; // PhiCfg<T> in svgd_kernels.hip
+                            cap.tile_pre = !f32;
+                            char name[8]; // (shorter than any name: the formatter must truncate)
+                            phi_plan_name(p, cap, name, (int)sizeof name);
+                            CHECK(std::strlen(name) == sizeof name - 1 && std::strncmp(name, "k_phi", 5) == 0);
+                            CHECK(p.dim == d && p.KP >= d && p.NCB >= 1 && p.NCB <= 5);
+                            CHECK(p.VW == 16 * p.NCB);
+                            // S1V exactly where d = 16 NCB; else room for the column of ones
+                            CHECK(p.s1v == (d == 16 * p.NCB));
+                            CHECK(p.VW >= d + (p.s1v ? 0 : 1));
+                            if (p.s1v) CHECK(cap.tile_s1v && !k.phi_s1v.set && (!f32 || cap.b3));
+                            if (!f32 && d <= 16) {
+                                CHECK(p.rows() && p.KP == cap.rows_kp && p.R == (d <= 8 ? 4 : 2) && p.rows_kind == 2);
+                                if (p.path == PHI_SYM) CHECK(d <= 8 && k.phi_sym.or_(1) != 0);
+                                if (k.phi_sym.set) CHECK((p.path == PHI_SYM) == (d <= 8 && k.phi_sym.v != 0));
+                                else CHECK((p.path == PHI_SYM) == (d <= 8 && n >= 32768 && n / world >= 8192));
+                            } else if (!f32) {
+                                CHECK(p.path == PHI_TILE_F64 && p.KP == KP);
+                            } else {
+                                CHECK(p.KP == KP);
+                                CHECK(p.path == PHI_TILE_F32 || p.path == PHI_F32S || p.path == PHI_B3);
+                                if (p.path != PHI_TILE_F32) CHECK(r0 % 16 == 0 && !k.phi_tile_generic && cap.f32s);
+                                if (p.path == PHI_B3) CHECK(cap.b3 && k.phi_b3.or_(1) != 0);
+                                if (p.path == PHI_TILE_F32) CHECK(r0 % 16 != 0 || k.phi_tile_generic || !cap.f32s);
+                                CHECK(p.b3_rg == (cap.b3 && !k.phi_tile_generic && k.phi_b3.or_(1) ? k.phi_b3_rg.or_(1) : 1));
+                            }
+                            CHECK(p.fused() == (p.path != PHI_TILE_F64 && p.path != PHI_TILE_F32));
+                        }
+    }
+}
+
 static void test_models_vs_oracle()
 {
     const int d = 5, k = 3;
@@ -163,6 +242,7 @@ static void test_oracle_paths()
 int main()
 {
     test_plan();
+    test_phi_plan();
     test_models_vs_oracle();
     test_oracle_paths();
     if (failures) {

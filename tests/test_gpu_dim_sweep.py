@@ -37,14 +37,13 @@ import pytest
 import svgdcpp_amd as S
 from svgdcpp_amd import _capi as C
 
+from _dispatch import F32_TABLE, F32_VARIANTS, F64_TABLE, KNOBS, knob_value
+from _dispatch import expected_name as _expected_name
+
 gpu = pytest.mark.gpu
 
 PHI_TOL = 1e-10
 F32_REL = 1e-4
-
-KNOBS = ("SVGD_PHI_SYM", "SVGD_PHI_B3", "SVGD_PHI_B3_RG", "SVGD_PHI_S1V", "SVGD_PHI_TILE_GENERIC",
-         "SVGD_COLLECT_FP64", "SVGD_MCOL_BF16", "SVGD_BUCKET_CAP", "SVGD_MEDIAN_SAMPLE",
-         "SVGD_MEDIAN_SIGMA")
 
 
 @pytest.fixture(autouse=True)
@@ -66,40 +65,7 @@ def _report(what, n, d, err, bar):
 
 
 # ------------------------------------------------------- 1. dispatch table --
-# (d_lo, d_hi, name); {d} is the dimension.  k_phi<T, KP, NCB, waves, prefetch,
-# S1V>: the fp64 build has 8 waves and the register prefetch, the fp32 one 4
-# waves and none (PhiCfg in svgd_kernels.hip).
-F64_TABLE = [
-    (1, 8, "k_phi_rows<{d}, 4, 8, 8192, 8>"),
-    (9, 16, "k_phi_rows<{d}, 2, 8, 8192, 8>"),
-    (17, 31, "k_phi<double, 32, 2, 8, true, false>"),
-    (32, 32, "k_phi<double, 32, 2, 8, true, true>"),
-    (33, 47, "k_phi<double, 64, 4, 8, true, false>"),
-    (48, 48, "k_phi<double, 64, 3, 8, true, true>"),
-    (49, 63, "k_phi<double, 64, 4, 8, true, false>"),
-    (64, 64, "k_phi<double, 64, 4, 8, true, true>"),
-]
-F32_TABLE = [
-    (1, 4, "k_phi<float, 4, 1, 4, false, false>"),
-    (5, 8, "k_phi<float, 8, 1, 4, false, false>"),
-    (9, 12, "k_phi<float, 12, 1, 4, false, false>"),
-    (13, 15, "k_phi_f32s<16, 1>"),
-    (16, 16, "k_phi_f32s<16, 2>"),
-    (17, 31, "k_phi_b3<32, 2, 8, false, 1>"),
-    (32, 32, "k_phi_b3<32, 2, 8, true, 1>"),
-    (33, 47, "k_phi_b3<64, 4, 8, false, 1>"),
-    (48, 48, "k_phi_b3<64, 3, 8, true, 1>"),
-    (49, 63, "k_phi_b3<64, 4, 8, false, 1>"),
-    (64, 64, "k_phi_b3<64, 4, 8, true, 1>"),
-]
-
-
-def _expected_name(table, d):
-    hits = [name.format(d=d) for lo, hi, name in table if lo <= d <= hi]
-    assert len(hits) == 1, (d, hits)  # the table covers 1..64 once
-    return hits[0]
-
-
+# (the tables: tests/_dispatch.py, also checked without a GPU by tests/test_phi_plan_cpu.py)
 @gpu
 @pytest.mark.parametrize("d", range(1, 65))
 @pytest.mark.parametrize("dtype,table", [(C.SVGD_F64, F64_TABLE), (C.SVGD_F32, F32_TABLE)],
@@ -110,6 +76,7 @@ def test_dispatch_table(dtype, table, d):
     name = c.phi_kernel_name()
     c.close()
     assert name == _expected_name(table, d)
+    assert name == S.plan_phi_name(d, 333, dtype)  # the context and the context-free plan agree
 
 
 # ------------------------------------------------ 2. fp64 row-stream phi ----
@@ -388,18 +355,6 @@ def test_tile_median_direct(oracle, d):
 
 
 # -------------------------------------------------------------- 7. F32 ------
-F32_VARIANTS = ([(d, None, None) for d in range(1, 65)] +
-                [(17, "SVGD_PHI_B3", "k_phi_f32s<32, 2>"), (31, "SVGD_PHI_B3", "k_phi_f32s<32, 2>"),
-                 (32, "SVGD_PHI_B3", "k_phi_f32s<32, 3>"), (48, "SVGD_PHI_B3", "k_phi_f32s<64, 4>"),
-                 (63, "SVGD_PHI_B3", "k_phi_f32s<64, 4>"), (64, "SVGD_PHI_B3", "k_phi_f32s<64, 5>"),
-                 (32, "SVGD_PHI_S1V", "k_phi_b3<32, 3, 8, false, 1>"),
-                 (48, "SVGD_PHI_S1V", "k_phi_b3<64, 4, 8, false, 1>"),
-                 (64, "SVGD_PHI_S1V", "k_phi_b3<64, 5, 8, false, 1>"),
-                 (12, "SVGD_PHI_TILE_GENERIC", "k_phi<float, 12, 1, 4, false, false>"),
-                 (16, "SVGD_PHI_TILE_GENERIC", "k_phi<float, 16, 2, 4, false, false>"),
-                 (32, "SVGD_PHI_TILE_GENERIC", "k_phi<float, 32, 3, 4, false, false>")])
-
-
 @gpu
 @pytest.mark.parametrize("d,knob,name", F32_VARIANTS,
                          ids=["%d-%s" % (d, {None: "default", "SVGD_PHI_B3": "b3off", "SVGD_PHI_S1V": "ones",
@@ -414,7 +369,7 @@ def test_f32_phi_every_d(oracle, monkeypatch, d, knob, name):
     streamed one is the default (SVGD_PHI_TILE_GENERIC=1)."""
     n = 333
     if knob:
-        monkeypatch.setenv(knob, "1" if knob == "SVGD_PHI_TILE_GENERIC" else "0")
+        monkeypatch.setenv(knob, knob_value(knob))
     X = oracle.splitmix((n, d), 3.0, 500 + n + d)
     G = oracle.splitmix((n, d), 1.0, 600 + n + d)
     a = float(np.log(n) / (2.0 * d * 3.0))  # typical median-heuristic magnitude

@@ -2680,40 +2680,76 @@ __global__ void k_prep_sym(const double *__restrict__ xc, int KP, const double *
     }
 }
 
-// One skew step: the lane's R rows against the column record at rj (LDS),
-// whose coordinates xj the previous step already loaded (PRE: after this
-// step's Gram, the next record's coordinates rn are loaded into xj -- their
-// LDS latency then hides behind this step's exp and accumulation instead of
-// stalling the next step's Gram; xj's registers are free after the Gram).
-// SYMM: also the column side into cacc; ROT: then rotate cacc one lane.
-#ifndef SVGD_SYM_PRE
-#define SVGD_SYM_PRE 1
-#endif
+// One skew step: the lane's R rows against the column record at LDS address
+// rj, whose coordinates xj the previous step already loaded.  LDS data
+// returns in issue order, so the reads are issued in the order of their use:
+// this record's W before the Gram (in flight behind it, needed after the
+// exp), the table reads as soon as their offsets exist, and last (NEXT) the
+// next record's coordinates into xj, free after the Gram and needed a whole
+// step later.  The table multiplies then wait with a counted lgkmcnt that
+// leaves the xj reads in flight.  The address rotates in place once the W
+// reads are issued (they took it at issue).
+// One s_waitcnt per group of uses (through the intrinsic, so the compiler's
+// own insertion sees it): left alone it waits before each 16-byte operand of
+// the Gram and each table value, 7 waits a step.
+// SYMM: also the column side into cacc; NEXT: a step follows, cacc rotates
+// one lane with the address.
+template <int N> __device__ __forceinline__ void sym_wait_lgkm()
+{
+    static_assert(N >= 0 && N < 16, "lgkmcnt range");
+    __builtin_amdgcn_s_waitcnt(0xC07F | (N << 8)); // gfx9: lgkmcnt in bits 11:8, the others at their maxima
+}
+typedef const __attribute__((address_space(3))) double lds_cdouble;
+typedef double sym_d2 __attribute__((ext_vector_type(2)));
+typedef const __attribute__((address_space(3))) sym_d2 lds_cd2;
 template <int D>
-__device__ __forceinline__ void sym_load_x(const double *rj, double (&xj)[D + (D & 1)])
+__device__ __forceinline__ void sym_load_x(uint32_t rj, double (&xj)[D + (D & 1)])
 {
     // 16-byte LDS reads of the lane's record (ds_read_b128: 16-lane groups,
     // the odd 16-byte record stride conflict-free).  The records are 16-byte
-    // aligned (SRS even, whole-KiB buffers), but without the hint the
-    // compiler emits ds_read2_b64 pairs, whose 32-bank rule puts records r
-    // and r + 8 on the same banks: every record read 2-way conflicted.
-    const double2 *r2 = reinterpret_cast<const double2 *>(__builtin_assume_aligned(rj, 16));
+    // aligned (SRS even, whole-KiB buffers); as 8-byte reads the compiler
+    // emits ds_read2_b64 pairs, whose 32-bank rule puts records r and r + 8
+    // on the same banks: every record read 2-way conflicted.
+    lds_cd2 *r2 = (lds_cd2 *)(uintptr_t)rj;
 #pragma unroll
     for (int q = 0; q < (D + 1) / 2; ++q) {
-        const double2 t = r2[q];
+        const sym_d2 t = r2[q];
         xj[2 * q] = t.x;
         xj[2 * q + 1] = t.y;
     }
 }
-template <int D, int R, bool SYMM, bool ROT, bool PRE>
-__device__ __forceinline__ void sym_step(const double *rj, const double *rn, double (&xj)[D + (D & 1)],
+template <int D, int R, bool SYMM, bool NEXT>
+__device__ __forceinline__ void sym_step(uint32_t &rj, double (&xj)[D + (D & 1)],
                                          const double (&xs)[R][D], const double (&wr)[R][D + 1],
                                          double (&acc)[R][D + 1], double (&cacc)[D + 1], const double *tab)
 {
     constexpr int DP = D + 1;
     __builtin_amdgcn_sched_barrier(0);
+    double wj[DP];
+    if constexpr (D % 2 == 0) { // W at a 16-byte boundary: D / 2 16-byte reads and one of 8
+        lds_cd2 *r2 = (lds_cd2 *)(uintptr_t)rj;
+#pragma unroll
+        for (int q = 0; q < D / 2; ++q) {
+            const sym_d2 t = r2[D / 2 + q];
+            wj[2 * q] = t.x;
+            wj[2 * q + 1] = t.y;
+        }
+    } else { // W[0] came with the coordinates (their last 16-byte read), the rest as above
+        wj[0] = xj[D];
+        lds_cd2 *r2 = (lds_cd2 *)(uintptr_t)rj;
+#pragma unroll
+        for (int q = 0; q < D / 2; ++q) {
+            const sym_d2 t = r2[(D + 1) / 2 + q];
+            wj[1 + 2 * q] = t.x;
+            wj[2 + 2 * q] = t.y;
+        }
+    }
+    wj[D] = ((lds_cdouble *)(uintptr_t)rj)[2 * D];
+    __builtin_amdgcn_sched_barrier(0);
+    sym_wait_lgkm<D / 2 + 1>(); // xj is in: only the W reads (D / 2 + 1 of them) are behind it
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (NEXT) rj = (uint32_t)dpp_ror15_i((int)rj);
     double u[R];
-    const double2 *r2 = reinterpret_cast<const double2 *>(__builtin_assume_aligned(rj, 16));
 #pragma unroll
     for (int r = 0; r < R; ++r) u[r] = fma(xs[r][0], xj[0], EXP_UB); // biased: u >= 0
 #pragma unroll
@@ -2721,19 +2757,6 @@ __device__ __forceinline__ void sym_step(const double *rj, const double *rn, dou
 #pragma unroll
         for (int r = 0; r < R; ++r) u[r] = fma(xs[r][k], xj[k], u[r]);
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (PRE) sym_load_x<D>(rn, xj);
-    double wj[DP + 1];
-    if constexpr (D % 2 == 0) { // W at a 16-byte boundary: (D + 2) / 2 reads
-#pragma unroll
-        for (int q = 0; q < (DP + 1) / 2; ++q) {
-            const double2 t = r2[D / 2 + q];
-            wj[2 * q] = t.x;
-            wj[2 * q + 1] = t.y;
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < DP; ++k) wj[k] = rj[D + k];
-    }
     double f[R], T[R], E[R];
     int ki[R];
 #pragma unroll
@@ -2743,8 +2766,12 @@ __device__ __forceinline__ void sym_step(const double *rj, const double *rn, dou
         T[r] = *reinterpret_cast<const double *>(reinterpret_cast<const char *>(tab) + tab8k_offset(ki[r]));
     }
     __builtin_amdgcn_sched_barrier(0);
+    if constexpr (NEXT) sym_load_x<D>(rj, xj);
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int r = 0; r < R; ++r) E[r] = exp2_4096_poly01(f[r]);
+    __builtin_amdgcn_sched_barrier(0);
+    sym_wait_lgkm<NEXT ? (D + 1) / 2 : 0>(); // the table values (and W before them) are in, the xj reads stay in flight
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int r = 0; r < R; ++r) E[r] = E[r] * tab_scale(T[r], ki[r]);
@@ -2758,7 +2785,7 @@ __device__ __forceinline__ void sym_step(const double *rj, const double *rn, dou
             double c = cacc[k];
 #pragma unroll
             for (int r = 0; r < R; ++r) c = fma(E[r], wr[r][k], c);
-            cacc[k] = ROT ? dpp_ror15(c) : c;
+            cacc[k] = NEXT ? dpp_ror15(c) : c;
         }
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -2779,33 +2806,22 @@ __device__ __forceinline__ void sym_phases(const char *cb, int grp, int tl, int 
 #pragma unroll 1
     for (int ph = 0; ph < 4; ++ph) {
         const int set = (grp + ph) & 3;
-        // this lane's record at step s: column (tl + s) & 15 of the set; the
-        // byte offset rotates with the column packet
-        int roff = (set * 16 + tl) * SRS * 8;
+        // this lane's record at step s: column (tl + s) & 15 of the set; its
+        // LDS address rotates with the column packet (the buffer base is
+        // uniform, so it is added once here, not after every rotation)
+        uint32_t ra = lds_addr(cb) + (set * 16 + tl) * SRS * 8;
         double cacc[DP];
 #pragma unroll
         for (int k = 0; k < DP; ++k) cacc[k] = 0.0;
         // 16 steps straight-line: the last one leaves the packet in place
         double xj[D + (D & 1)];
-        sym_load_x<D>(reinterpret_cast<const double *>(cb + roff), xj);
+        sym_load_x<D>(ra, xj);
 #pragma unroll
         for (int s = 0; s < 16; ++s) {
-            if (s < 15) {
-                const int rnext = dpp_ror15_i(roff);
-                if constexpr (SVGD_SYM_PRE) {
-                    sym_step<D, R, SYMM, true, true>(reinterpret_cast<const double *>(cb + roff),
-                                                     reinterpret_cast<const double *>(cb + rnext), xj, xs, wr,
-                                                     acc, cacc, tab);
-                } else {
-                    sym_step<D, R, SYMM, true, false>(reinterpret_cast<const double *>(cb + roff), nullptr, xj,
-                                                      xs, wr, acc, cacc, tab);
-                    sym_load_x<D>(reinterpret_cast<const double *>(cb + rnext), xj);
-                }
-                roff = rnext;
-            } else {
-                sym_step<D, R, SYMM, false, false>(reinterpret_cast<const double *>(cb + roff), nullptr, xj, xs,
-                                                   wr, acc, cacc, tab);
-            }
+            if (s < 15)
+                sym_step<D, R, SYMM, true>(ra, xj, xs, wr, acc, cacc, tab);
+            else
+                sym_step<D, R, SYMM, false>(ra, xj, xs, wr, acc, cacc, tab);
         }
         if constexpr (SYMM) {
             // lane t holds column (t - 1) & 15's sum over this group's rows;
@@ -2902,9 +2918,18 @@ __global__ __launch_bounds__(SYM_NW * 64) __attribute__((amdgpu_waves_per_eu(2, 
         const char *src =
             reinterpret_cast<const char *>(srec + (c.J * B + (int64_t)c.q * SYM_SUB) * SRS);
         char *dst = smem + buf * SUBB;
+        // The DMA as the builtin emits it, but out of the compiler's sight:
+        // a pending one it knows of makes it drain the DMA at the phases'
+        // first LDS read and turn every counted lgkmcnt after it into
+        // lgkmcnt(0).  The loop waits for the DMA itself (wait_vmcnt<0> and
+        // the barrier before the buffer is read).
+        uint32_t m0_keep;
         for (int p = w; p < NP; p += SYM_NW)
-            __builtin_amdgcn_global_load_lds((gbl_void *)(src + p * 1024 + lane * 16),
-                                             (lds_void *)(dst + p * 1024), 16, 0, 0);
+            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
+                         "global_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
+                         : "=&s"(m0_keep)
+                         : "s"(lds_addr(dst + p * 1024)), "v"(src + p * 1024 + lane * 16)
+                         : "memory");
     };
 
     double xs[R][D], wr[R][DP], acc[R][DP];
@@ -3006,10 +3031,12 @@ __global__ __launch_bounds__(SYM_NW * 64) __attribute__((amdgpu_waves_per_eu(2, 
             wait_vmcnt<0>(); // (rare: once per row block) also drains the next sub-tile's DMA
         }
         const char *cb = smem + buf * SUBB;
-        // one code path for both tile kinds (two would double the live
-        // register ranges: the allocator spilled); a diagonal tile's column
-        // sums are computed and dropped -- its row side already holds every
-        // ordered pair of the square (~2 % of the tiles)
+        // one code path for both tile kinds: with a row-side-only body for
+        // the diagonal units behind a uniform branch the allocator spills
+        // inside the off-diagonal body's 16-step block (d = 8: ~280 scratch
+        // accesses per phase); a diagonal tile's column sums are computed
+        // and dropped -- its row side already holds every ordered pair of
+        // the square (~2 % of the tiles)
         sym_phases<D, true>(cb, grp, tl, w, xs, wr, acc, sCol + buf * SCOL, tab);
     }
     sym_lds_barrier(); // every wave's column sums of the last sub-tile are in LDS

@@ -1,16 +1,16 @@
 # Top-level build of the MI355X (gfx950) SVGD library and test/bench helpers.
 #   make            -> svgdcpp_amd/libsvgdcpp_amd.so (HIP kernels + C ABI, links RCCL)
 #   make oracle     -> oracle/liboracle.so (CPU restatement; test infrastructure)
-#   make cpp        -> build/{mvn_example,gmm_example,svgd_run_bench,test_api,test_dist,test_ksd} (SVGDCpp-compatible C++ API)
+#   make cpp        -> build/{mvn_example,gmm_example,svgd_run_bench,test_api,test_dist,test_ksd,test_glm} (SVGDCpp-compatible C++ API)
 HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 HIPFLAGS ?= -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wall -Wno-unused-result
 SRC_DIR := svgdcpp_amd/csrc
 LIB := svgdcpp_amd/libsvgdcpp_amd.so
 OBJS := $(SRC_DIR)/svgd_kernels.o $(SRC_DIR)/svgd_collect.o $(SRC_DIR)/svgd_ksd.o $(SRC_DIR)/svgd_capi.o $(SRC_DIR)/plan.o $(SRC_DIR)/host_models.o \
-        $(SRC_DIR)/hostcomm.o
+        $(SRC_DIR)/hostcomm.o $(SRC_DIR)/svgd_glm.o $(SRC_DIR)/host_glm.o
 HDRS := $(SRC_DIR)/svgd_kernels.h $(SRC_DIR)/plan.h $(SRC_DIR)/svgd_ksd.h $(SRC_DIR)/svgd_device.h $(SRC_DIR)/svgd_exp_table.h \
-        include/svgdcpp_amd/svgd_capi.h
+        $(SRC_DIR)/svgd_glm.h $(SRC_DIR)/host_glm.h include/svgdcpp_amd/svgd_capi.h
 
 all: $(LIB)
 
@@ -35,6 +35,9 @@ $(SRC_DIR)/hostcomm.o: $(SRC_DIR)/hostcomm.cpp $(SRC_DIR)/hostcomm.h
 $(SRC_DIR)/host_models.o: $(SRC_DIR)/host_models.cpp $(SRC_DIR)/host_grad_block.inc $(SRC_DIR)/host_grad_soa8.inc $(HDRS)
 	$(CXX) -O3 -std=c++17 -fPIC -fopenmp -Wall -Wno-psabi -c $< -o $@
 
+$(SRC_DIR)/host_glm.o: $(SRC_DIR)/host_glm.cpp $(HDRS)
+	$(CXX) -O3 -std=c++17 -fPIC -fopenmp -Wall -c $< -o $@
+
 $(LIB): $(OBJS)
 	$(HIPCC) -shared --offload-arch=$(ARCH) -o $@ $(OBJS) -L/opt/rocm/lib -lrccl -fopenmp -Wl,-rpath,/opt/rocm/lib
 
@@ -45,7 +48,7 @@ oracle:
 CPP_FLAGS := -O2 -std=c++17 -Wall -fopenmp -Iinclude
 CPP_LINK := -Lsvgdcpp_amd -lsvgdcpp_amd -Wl,-rpath,'$$ORIGIN/../svgdcpp_amd' -Wl,--allow-shlib-undefined
 CPP_HDRS := $(wildcard include/SVGDCpp/*.hpp include/SVGDCpp/*/*.hpp) include/Core include/Model include/Kernel include/Optimizer
-CPP_BINS := build/mvn_example build/gmm_example build/svgd_run_bench build/test_api build/test_dist build/test_ksd
+CPP_BINS := build/mvn_example build/gmm_example build/svgd_run_bench build/test_api build/test_dist build/test_ksd build/test_glm
 
 cpp: $(CPP_BINS) build/host_grad_bench
 
@@ -70,6 +73,10 @@ build/test_ksd: tests/cpp/test_ksd.cpp $(CPP_HDRS) $(LIB)
 	@mkdir -p build
 	$(CXX) $(CPP_FLAGS) $< -o $@ $(CPP_LINK)
 
+build/test_glm: tests/cpp/test_glm.cpp $(CPP_HDRS) $(LIB)
+	@mkdir -p build
+	$(CXX) $(CPP_FLAGS) $< -o $@ $(CPP_LINK)
+
 # Host-code sanitizers (ASan + UBSan): planner, host models and the CPU oracle
 # linked into a self-checking driver (the HIP host code needs a GPU: see
 # tests/cpp/sanitize_host.cpp).  Run by tests/test_sanitize.py.
@@ -84,8 +91,17 @@ build/sanitize_host: tests/cpp/sanitize_host.cpp $(SRC_DIR)/plan.cpp $(SRC_DIR)/
 sanitize: build/sanitize_host
 	ASAN_OPTIONS=detect_leaks=1 OMP_NUM_THREADS=2 ./build/sanitize_host
 
+# the host GLM (host_glm.cpp) under the same sanitizers, with a driver of its
+# own (tests/cpp/sanitize_glm.cpp).  Run by tests/test_sanitize_glm.py.
+build/sanitize_glm: tests/cpp/sanitize_glm.cpp $(SRC_DIR)/host_glm.cpp $(SRC_DIR)/host_glm.h include/svgdcpp_amd/svgd_capi.h
+	@mkdir -p build
+	$(CXX) -O1 -g -std=c++17 -fopenmp $(SAN) tests/cpp/sanitize_glm.cpp $(SRC_DIR)/host_glm.cpp -o $@ -lm
+
+sanitize_glm: build/sanitize_glm
+	ASAN_OPTIONS=detect_leaks=1 OMP_NUM_THREADS=2 ./build/sanitize_glm
+
 clean:
-	rm -f $(OBJS) $(LIB) $(CPP_BINS) build/sanitize_host
+	rm -f $(OBJS) $(LIB) $(CPP_BINS) build/sanitize_host build/sanitize_glm
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle cpp clean sanitize
+.PHONY: all oracle cpp clean sanitize sanitize_glm

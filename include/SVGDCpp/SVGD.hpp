@@ -55,6 +55,7 @@
 #include "Kernel/Kernel.hpp"
 #include "Model/Model.hpp"
 #include "Model/MultivariateNormal.hpp"
+#include "Model/GeneralizedLinearModel.hpp"
 #include "Optimizer/Optimizer.hpp"
 
 /** SVGD.hpp:27-52 (+ Device, ComputeDtype, World / Rank / UniqueId). */
@@ -284,8 +285,11 @@ public:
         };
         const double *X = coord_matrix_ptr_->data();
         check(svgd_set_particles(c, X));
+        // the device score when this context mirrors the model (Initialize)
+        const bool device_score = c == ctx_.get() && initialized_ && UsesDeviceModelStep();
         std::vector<double> G((size_t)std::max<int64_t>(1, r1 - r0) * dimension_);
-        model_ptr_->LogModelGradBatch(X + (size_t)r0 * dimension_, r1 - r0, G.data());
+        if (!device_score)
+            model_ptr_->LogModelGradBatch(X + (size_t)r0 * dimension_, r1 - r0, G.data());
         double a = 0.0;
         if (rbf_ptr_ && rbf_ptr_->GetScaleMethod() == GaussianRBFKernel::ScaleMethod::Constant &&
             rbf_ptr_->IsIsotropic())
@@ -293,7 +297,14 @@ public:
         else
             check(svgd_median_scale(c, &a, nullptr));
         double v = 0.0, u = 0.0;
-        check(svgd_ksd(c, G.data(), a, &v, &u, nullptr));
+        if (device_score)
+        {
+            const GeneralizedLinearModel &glm = static_cast<const GeneralizedLinearModel &>(*model_ptr_);
+            check(svgd_set_device_glm_batch(c, glm.BatchBegin(), glm.BatchCount()));
+            device_m0_ = glm.BatchBegin();
+            device_count_ = glm.BatchCount();
+        }
+        check(svgd_ksd(c, device_score ? nullptr : G.data(), a, &v, &u, nullptr));
         return unbiased ? u : v;
     }
 
@@ -319,6 +330,21 @@ public:
         return rbf_ptr_->GetScaleMethod() != GaussianRBFKernel::ScaleMethod::Hessian;
     }
 
+    /** True when Step() runs wholly on the device, grad log p included
+     *  (svgd_step(ctx, NULL) with the model mirrored by svgd_set_device_glm):
+     *  a model of exactly the GeneralizedLinearModel type (a subclass keeps
+     *  the split calls), the Median or Constant scale, no matrix logging
+     *  (which reads X_t and G from the host buffers). */
+    bool UsesDeviceModelStep() const
+    {
+        if (!UsesDevicePath() || log_intermediate_matrices_)
+            return false;
+        const Model &m = *model_ptr_;
+        if (typeid(m) != typeid(GeneralizedLinearModel))
+            return false;
+        return rbf_ptr_->GetScaleMethod() != GaussianRBFKernel::ScaleMethod::Hessian;
+    }
+
     /** Rows [row0, row1) of the particles this rank steps (all of them on one GPU). */
     int64_t ShardBegin() const { return row0_; }
     int64_t ShardEnd() const { return row1_; }
@@ -335,6 +361,18 @@ protected:
         if (UsesPipelinedStep())
         {
             Check(svgd_step_host_model(c, model_ptr_->HostModelHandle()));
+            return;
+        }
+        if (UsesDeviceModelStep())
+        {
+            const GeneralizedLinearModel &glm = static_cast<const GeneralizedLinearModel &>(*model_ptr_);
+            if (glm.BatchBegin() != device_m0_ || glm.BatchCount() != device_count_)
+            { // the window moved since the last step
+                Check(svgd_set_device_glm_batch(c, glm.BatchBegin(), glm.BatchCount()));
+                device_m0_ = glm.BatchBegin();
+                device_count_ = glm.BatchCount();
+            }
+            Check(svgd_step(c, nullptr));
             return;
         }
         const int64_t rows = row1_ - row0_;
@@ -475,6 +513,13 @@ protected:
         Check(svgd_set_optimizer(c, optimizer_ptr_->Kind(), p[0], p[1], p[2], p[3]));
         Check(check_bounds_ ? svgd_set_bounds(c, lower_.data(), upper_.data()) : svgd_set_bounds(c, nullptr, nullptr));
         ConfigureScale();
+        if (UsesDeviceModelStep())
+        {
+            GeneralizedLinearModel &glm = static_cast<GeneralizedLinearModel &>(*model_ptr_);
+            Check(svgd_set_device_glm(c, glm.GlmHandle()));
+            device_m0_ = glm.BatchBegin();
+            device_count_ = glm.BatchCount();
+        }
     }
 
     void ConfigureScale()
@@ -573,6 +618,7 @@ protected:
     int log_precision_ = 0;
     int device_ = 0;
     int64_t row0_ = 0, row1_ = 0;
+    int64_t device_m0_ = 0, device_count_ = 0; // the device GLM's window (UsesDeviceModelStep)
     std::vector<double> lower_, upper_;
     std::shared_ptr<Kernel> kernel_ptr_;
     std::shared_ptr<GaussianRBFKernel> rbf_ptr_;

@@ -299,6 +299,51 @@ int svgd_set_device_model(svgd_ctx *ctx, const void *model);
  * (shard layout like svgd_get_shard). */
 int svgd_device_logp_grad(svgd_ctx *ctx, double *G_shard_out);
 
+/* ---- generalized linear model posterior (extension) ----------------------
+ * Bayesian logistic / linear regression on data A (m x dim, row-major) and
+ * y (m), prior N(0, I / prior_prec), for theta = one particle:
+ *   z_j   = a_j . theta
+ *   log p = s (m/B) sum_j l(y_j, z_j) - (prior_prec / 2) |theta|^2
+ *   grad  = s (m/B) sum_j r(y_j, z_j) a_j - prior_prec theta
+ *   SVGD_GLM_LOGISTIC  l = y z - log(1 + e^z),  r = y - sigma(z),  y in [0, 1]
+ *   SVGD_GLM_GAUSSIAN  l = -(y - z)^2 / 2,      r = y - z
+ * s = lik_scale > 0 (the 1/sigma^2 of the Gaussian link, or a tempering
+ * factor); the sums run over the batch window [m0, m0 + B) of the data rows
+ * (all m rows until svgd_glm_set_batch), scaled by m / B.  The data are
+ * copied.  Refused: NULL pointers, an unknown link, non-finite data,
+ * logistic labels outside [0, 1], s <= 0, prior_prec < 0 (SVGD_ERR_ARG);
+ * dim < 1 or m < 1 (SVGD_ERR_DIM). */
+#define SVGD_GLM_LOGISTIC 0
+#define SVGD_GLM_GAUSSIAN 1
+int svgd_glm_create(void **model, int dim, int64_t m, const double *A, const double *y, int link,
+                    double lik_scale, double prior_prec);
+int svgd_glm_destroy(void *model);
+/* The batch window [m0, m0 + count) of the data rows; SVGD_ERR_ARG unless
+ * m0 >= 0, count >= 1 and m0 + count <= m.  (The caller shuffles its data
+ * once and moves the window: there is no random selection here.) */
+int svgd_glm_set_batch(void *model, int64_t m0, int64_t count);
+/* out[i] = log p(X[i]) for nrows particles (OpenMP over rows). */
+int svgd_glm_logp(void *model, const double *X, int64_t nrows, double *out);
+/* G[i] = grad log p(X[i]) for nrows particles (OpenMP over rows; each row's
+ * sum in data order, so the result does not depend on the thread count). */
+int svgd_glm_logp_grad(void *model, const double *X, int64_t nrows, double *G);
+/* H = sum_i -hess log p(x_i) over nrows particles (d x d, row-major), the
+ * sum of the Hessian scale: sum_i [ s (m/B) sum_j w_ij a_j a_j^T +
+ * prior_prec I ], w = sigma (1 - sigma) (logistic) or 1 (Gaussian). */
+int svgd_glm_neg_hess_sum(void *model, const double *X, int64_t nrows, double *H);
+/* Mirror a GLM (svgd_glm_create) on the device: the data are uploaded once
+ * (every rank holds all m rows; only particles are sharded) and the model's
+ * current batch window is taken over.  Afterwards svgd_step(ctx, NULL),
+ * svgd_device_logp_grad and svgd_ksd(ctx, NULL, ...) evaluate grad log p on
+ * the device, in fp64 whatever the context's dtype; two calls on the same
+ * state return the same bits.  A context holds one device model: this call
+ * removes a Gaussian-sum mirror and svgd_set_device_model removes this one.
+ * NULL removes it.  d <= 64. */
+int svgd_set_device_glm(svgd_ctx *ctx, const void *glm);
+/* Move the device GLM's batch window (no data is copied); SVGD_ERR_UNSET
+ * without a device GLM, SVGD_ERR_ARG for a window outside the data. */
+int svgd_set_device_glm_batch(svgd_ctx *ctx, int64_t m0, int64_t count);
+
 /* Kernelized Stein discrepancy of the current particles with the isotropic
  * RBF kernel k = exp(-a |x - y|^2), whatever scale method the context steps
  * with.  For s_i = grad log p(x_i), r = x_i - x_j:

@@ -30,6 +30,8 @@ SVGD_SCALE_MEDIAN = 0
 SVGD_SCALE_FIXED = 2
 SVGD_SCALE_MATRIX = 3
 SVGD_SCALE_HESSIAN = 1
+SVGD_GLM_LOGISTIC = 0
+SVGD_GLM_GAUSSIAN = 1
 SVGD_MEDIAN_DIRECT = 0
 SVGD_MEDIAN_BRACKET = 1
 SVGD_MEDIAN_FALLBACK = 2
@@ -108,6 +110,15 @@ SIGNATURES = {
     "svgd_model_destroy": (ctypes.c_int, [_P]),
     "svgd_model_logp_grad": (ctypes.c_int, [_P, _D, _I64, _D]),
     "svgd_model_neg_hess_sum": (ctypes.c_int, [_P, _D, _I64, _D]),
+    "svgd_glm_create": (ctypes.c_int, [ctypes.POINTER(_P), ctypes.c_int, _I64, _D, _D, ctypes.c_int,
+                                       ctypes.c_double, ctypes.c_double]),
+    "svgd_glm_destroy": (ctypes.c_int, [_P]),
+    "svgd_glm_set_batch": (ctypes.c_int, [_P, _I64, _I64]),
+    "svgd_glm_logp": (ctypes.c_int, [_P, _D, _I64, _D]),
+    "svgd_glm_logp_grad": (ctypes.c_int, [_P, _D, _I64, _D]),
+    "svgd_glm_neg_hess_sum": (ctypes.c_int, [_P, _D, _I64, _D]),
+    "svgd_set_device_glm": (ctypes.c_int, [_P, _P]),
+    "svgd_set_device_glm_batch": (ctypes.c_int, [_P, _I64, _I64]),
 }
 
 _lib = None

@@ -388,6 +388,108 @@ def _gaussian_components(m):
     return None
 
 
+class GeneralizedLinearModel(Model):
+    """Posterior of Bayesian logistic / linear regression (extension): data
+    A (M, d) and y (M), prior N(0, I / prior_prec), for a particle theta
+
+        log p = s (M/B) sum_m l(y_m, a_m . theta) - (prior_prec / 2) |theta|^2
+
+    with l = y z - log(1 + e^z) (link="logistic", y in [0, 1]) or
+    l = -(y - z)^2 / 2 (link="gaussian"), s = lik_scale, and the sum over the
+    batch window [m0, m0 + B) of the rows (set_batch; all rows by default).
+    Evaluated by the C++ host model (svgd_glm_*); Context.set_device_model
+    mirrors it on the device."""
+
+    LINKS = {"logistic": C.SVGD_GLM_LOGISTIC, "gaussian": C.SVGD_GLM_GAUSSIAN}
+
+    def __init__(self, A, y, link="logistic", lik_scale=1.0, prior_prec=1.0):
+        A = np.ascontiguousarray(A, dtype=np.float64)
+        y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+        if A.ndim != 2 or A.shape[0] != y.shape[0]:
+            raise DimensionMismatchException("GLM data: A must be (M, d) and y (M).")
+        if link not in self.LINKS:
+            raise ValueError(PREFIX + "[Argument Error] GLM link must be 'logistic' or 'gaussian'.")
+        super().__init__(A.shape[1])
+        self.link_ = link
+        self.num_rows_ = A.shape[0]
+        self.batch_ = (0, self.num_rows_)
+        self._handle = None
+        h = ctypes.c_void_p()
+        rc = C.lib().svgd_glm_create(ctypes.byref(h), A.shape[1], A.shape[0], C.dptr(A), C.dptr(y),
+                                     self.LINKS[link], float(lik_scale), float(prior_prec))
+        if rc == C.SVGD_ERR_DIM:
+            raise DimensionMismatchException("GLM data: at least one row and one column are needed.")
+        if rc != C.SVGD_OK:
+            raise ValueError(PREFIX + "[Argument Error] GLM: the data must be finite, logistic labels in "
+                             "[0, 1], lik_scale > 0 and prior_prec >= 0.")
+        self._handle = h
+
+    def __del__(self):
+        try:
+            if getattr(self, "_handle", None):
+                C.lib().svgd_glm_destroy(self._handle)
+                self._handle = None
+        except Exception:
+            pass
+
+    def __copy__(self):
+        raise TypeError("a GeneralizedLinearModel owns its C handle and is not copied")
+
+    def set_batch(self, m0, count):
+        """The batch window [m0, m0 + count) of the data rows."""
+        if C.lib().svgd_glm_set_batch(self._handle, int(m0), int(count)) != C.SVGD_OK:
+            raise ValueError(PREFIX + "[Argument Error] Batch window outside the data.")
+        self.batch_ = (int(m0), int(count))
+
+    def _rows(self, X):
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        if X.ndim != 2 or X.shape[1] != self.dimension_:
+            raise DimensionMismatchException("Particle rows do not match the model dimension.")
+        return X
+
+    def log_model(self, X):
+        X = self._rows(X)
+        out = np.empty(X.shape[0])
+        C.lib().svgd_glm_logp(self._handle, C.dptr(X), X.shape[0], C.dptr(out))
+        return out
+
+    def log_model_grad(self, X, out=None):
+        X = self._rows(X)
+        G = out if out is not None else np.empty_like(X)
+        C.lib().svgd_glm_logp_grad(self._handle, C.dptr(X), X.shape[0], C.dptr(G))
+        return G
+
+    def log_model_grad_ptr(self, x_ptr, n, g_ptr):
+        C.lib().svgd_glm_logp_grad(self._handle, x_ptr, n, g_ptr)
+
+    def neg_hess_sum(self, X):
+        X = self._rows(X)
+        H = np.empty((self.dimension_, self.dimension_))
+        C.lib().svgd_glm_neg_hess_sum(self._handle, C.dptr(X), X.shape[0], C.dptr(H))
+        return H
+
+    def EvaluateLogModel(self, x):
+        return float(self.log_model(np.asarray(x, dtype=np.float64).reshape(1, -1))[0])
+
+    def EvaluateModel(self, x):
+        return math.exp(self.EvaluateLogModel(x))
+
+    def EvaluateLogModelGrad(self, x):
+        return self.log_model_grad(np.asarray(x, dtype=np.float64).reshape(1, -1))[0]
+
+    def EvaluateLogModelHessian(self, x):
+        return -self.neg_hess_sum(np.asarray(x, dtype=np.float64).reshape(1, -1))
+
+
+def _builtin_glm(model):
+    """The model's gradient is the built-in C++ GLM one (the _builtin_grad
+    rule: a subclass that overrides a gradient method runs as written)."""
+    t = type(model)
+    return (isinstance(model, GeneralizedLinearModel)
+            and t.log_model_grad is GeneralizedLinearModel.log_model_grad
+            and t.EvaluateLogModelGrad is GeneralizedLinearModel.EvaluateLogModelGrad)
+
+
 # ----------------------------------------------------------------- kernels --
 
 class Kernel:
@@ -796,7 +898,7 @@ class Context:
             H = (model.neg_hess_sum_ptr(self.x_host_ptr, nr) if _builtin_hess(model)
                  else model.neg_hess_sum(self.x_host[:nr]))
             self.set_step_hessian_sum(H)
-        if _builtin_grad(model):
+        if _builtin_grad(model) or _builtin_glm(model):
             model.log_model_grad_ptr(self.x_host_ptr, nr, self.g_host_ptr)
         elif nr > 0:
             self.g_host[:nr] = model.log_model_grad(self.x_host[:nr])
@@ -817,11 +919,24 @@ class Context:
 
     def set_device_model(self, model):
         """Mirror a GaussianSum on the device; then
-        step_device() runs the whole step, grad log p included, in HBM."""
-        if model is not None and not _builtin_grad(model):
-            raise TypeError("only the built-in Gaussian-sum models have a device form")
-        self.check(self.lib.svgd_set_device_model(self.h, model._handle if model is not None else None))
+        step_device() runs the whole step, grad log p included, in HBM.
+        A GeneralizedLinearModel is mirrored with its data and its current
+        batch window (svgd_set_device_glm); a context holds one device model,
+        None removes it."""
+        if model is not None and not (_builtin_grad(model) or _builtin_glm(model)):
+            raise TypeError("only the built-in Gaussian-sum and generalized linear models have a device form")
+        if model is None:
+            self.check(self.lib.svgd_set_device_model(self.h, None))
+            self.check(self.lib.svgd_set_device_glm(self.h, None))
+        elif _builtin_glm(model):
+            self.check(self.lib.svgd_set_device_glm(self.h, model._handle))
+        else:
+            self.check(self.lib.svgd_set_device_model(self.h, model._handle))
         self._device_model = model  # keep the host handle alive
+
+    def set_device_batch(self, m0, count):
+        """Move the device GLM's batch window to the data rows [m0, m0 + count)."""
+        self.check(self.lib.svgd_set_device_glm_batch(self.h, int(m0), int(count)))
 
     def device_logp_grad(self):
         out = np.empty((self.row1 - self.row0, self.dim), dtype=np.float64)
@@ -956,7 +1071,19 @@ class SVGD:
             c.set_scale(C.SVGD_SCALE_HESSIAN, 0.0)
         else:
             c.set_scale(C.SVGD_SCALE_MEDIAN, 0.0)
+        if self.UsesDeviceModelStep():
+            c.set_device_model(self.model_)
+            self._device_batch = self.model_.batch_
         self._initialized = True
+
+    def UsesDeviceModelStep(self):
+        """The whole step, grad log p included, runs on the device
+        (svgd_step(ctx, NULL)): a model of exactly the built-in GLM type, an
+        RBF kernel on the device path with a Median or Constant scale, and no
+        matrix logging (which reads X_t and G from the host buffers)."""
+        return (self.ctx is not None and type(self.model_) is GeneralizedLinearModel
+                and self.kernel_.scale_method_ != GaussianRBFKernel.ScaleMethod.Hessian
+                and not self.log_)
 
     def Run(self):
         """SVGD.hpp:338-366; coordinates are read from / written back to the
@@ -972,9 +1099,15 @@ class SVGD:
         c.set_particles(np.ascontiguousarray(self.coord_matrix_.T))
         hess = self.kernel_.scale_method_ == GaussianRBFKernel.ScaleMethod.Hessian
         hmodel = self.kernel_.target_model_ if hess else None
+        device_model = self.UsesDeviceModelStep()
         for _ in range(self.num_iterations_):
             self.model_.Step()
-            if hess and hmodel is not self.model_:
+            if device_model:
+                if self.model_.batch_ != self._device_batch:  # the window moved since the last step
+                    c.set_device_batch(*self.model_.batch_)
+                    self._device_batch = self.model_.batch_
+                c.step_device()
+            elif hess and hmodel is not self.model_:
                 # the kernel's own model supplies the Hessian (GaussianRBFKernel.hpp:202)
                 c.check(c.lib.svgd_begin_step(c.h, c.x_host_ptr))
                 nr = c.row1 - c.row0

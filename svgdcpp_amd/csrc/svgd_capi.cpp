@@ -30,8 +30,10 @@
 #include "svgd_kernels.h"
 #include "plan.h"
 #include "svgd_ksd.h"
+#include "svgd_glm.h"
 #include "hostcomm.h"
 #include "host_models.h"
+#include "host_glm.h"
 
 using namespace svgd_amd;
 
@@ -161,6 +163,18 @@ struct svgd_ctx {
     // device mirror of a built-in Gaussian-sum model (svgd_set_device_model)
     int dm_k = 0;
     double *dm_mu = nullptr, *dm_prec = nullptr;
+    // device mirror of a generalized linear model (svgd_set_device_glm); at
+    // most one of the two device models is set (dm_k > 0 or glm.m > 0)
+    struct Glm {
+        int64_t m = 0;                // data rows (0: no device GLM)
+        int link = 0;
+        double lik_scale = 1, prior_prec = 0;
+        int64_t m0 = 0, count = 0;    // batch window
+        double *rec = nullptr;        // glm_padded(m) records of glm_rec_stride(d) doubles
+        double *part = nullptr;       // smax x ldp x d partial sums
+        int smax = 1;                 // data splits that fill the device at most twice
+        int64_t ldp = 0;
+    } glm;
     int64_t row0 = 0, row1 = 0, nrows = 0, chunk = 0;
     Knobs knobs;  // the environment, read once at creation (read_knobs)
     PhiPlan plan; // the phi kernel of this context and its launch parameters (plan_phi)
@@ -2318,7 +2332,7 @@ int svgd_destroy(svgd_ctx *c)
                        c->m,     c->v,     c->lower,   c->upper, c->partial, c->scal, c->rec,
                        c->part,  c->dm_mu, c->dm_prec, c->sc_src, c->sc_M, c->sc_L, c->wv, c->zc,
                        c->sc_sgn,  c->sc_work, c->bak, c->srec, c->rowpart, c->colpart, c->contrib,
-                       c->xrecv_buf, c->tab8k,
+                       c->xrecv_buf, c->tab8k, c->glm.rec, c->glm.part,
                        c->ksd.G, c->ksd.mu, c->ksd.mpart, c->ksd.rec, c->ksd.xt, c->ksd.vt, c->ksd.nrm,
                        c->ksd.cvec, c->ksd.diag, c->ksd.part, c->ksd.rows, c->ksd.bpart, c->ksd.out};
     float *fbufs[] = {c->xcf, c->nrmf, c->cvf, c->Vf, c->zcf, c->XS, c->VS};
@@ -2764,6 +2778,30 @@ int svgd_step_host_model(svgd_ctx *c, const void *model)
     return rc;
 }
 
+namespace {
+
+bool has_device_model(const svgd_ctx *c) { return c->dm_k > 0 || c->glm.m > 0; }
+
+// grad log p of the device model -- the Gaussian sum or the GLM, whichever is
+// set -- at `rows` particles X (stride d) -> G, fp64, on the context's stream
+int launch_device_model_grad(svgd_ctx *c, const double *X, int64_t rows, double *G)
+{
+    if (c->glm.m > 0) {
+        const svgd_ctx::Glm &g = c->glm;
+        const int S = (int)std::min<int64_t>(g.smax, glm_tiles(g.count));
+        HIPCHK(c, launch_glm_pass(c->dim, g.link, X, rows, g.rec, g.m0, g.count, S, g.part, g.ldp,
+                                  c->stream));
+        HIPCHK(c, launch_glm_finish(c->dim, X, rows, g.part, S, g.ldp,
+                                    g.lik_scale * ((double)g.m / (double)g.count), g.prior_prec, G,
+                                    c->stream));
+        return SVGD_OK;
+    }
+    HIPCHK(c, launch_gauss_grad(X, rows, c->dim, c->dm_k, c->dm_mu, c->dm_prec, G, c->stream));
+    return SVGD_OK;
+}
+
+} // namespace
+
 int svgd_step(svgd_ctx *c, const double *G_shard)
 {
     if (G_shard) {
@@ -2772,12 +2810,12 @@ int svgd_step(svgd_ctx *c, const double *G_shard)
     }
     // fully device-resident step: grad log p from the device model
     CHK(check_ready(c));
-    if (c->dm_k == 0)
+    if (!has_device_model(c))
         return fail(c, SVGD_ERR_ARG,
                     "[Argument Error] Null log-gradient buffer and no device model set.");
     CHK(svgd_begin_step(c, nullptr));
-    HIPCHK(c, launch_gauss_grad(c->X + (size_t)c->row0 * c->dim, c->nrows, c->dim, c->dm_k,
-                                c->dm_mu, c->dm_prec, c->G + (size_t)c->row0 * c->dim, c->stream));
+    CHK(launch_device_model_grad(c, c->X + (size_t)c->row0 * c->dim, c->nrows,
+                                 c->G + (size_t)c->row0 * c->dim));
     c->mark = nullptr; // (the gradient kernel runs after the median's end event)
     CHK(scale_finish(c));
     CHK(allgather_rows(c, c->G));
@@ -2806,6 +2844,72 @@ int svgd_set_device_model(svgd_ctx *c, const void *model)
                              hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->dm_k = m->k;
+    c->glm.m = 0; // the two device models exclude each other
+    return SVGD_OK;
+}
+
+int svgd_set_device_glm(svgd_ctx *c, const void *glm)
+{
+    if (!c) return SVGD_ERR_ARG;
+    CHK(resolve_pending(c));
+    if (!glm) {
+        c->glm.m = 0;
+        return SVGD_OK;
+    }
+    const HostGlm *m = static_cast<const HostGlm *>(glm);
+    if (m->d != c->dim)
+        return fail(c, SVGD_ERR_DIM, "[Dimension Error] Model dimension does not match the particles.");
+    if (m->d > 64)
+        return fail(c, SVGD_ERR_ARG, "[Argument Error] Device model supports d <= 64.");
+    HIPCHK(c, hipSetDevice(c->device));
+    svgd_ctx::Glm &g = c->glm;
+    g.m = 0;
+    const int d = m->d, RS = glm_rec_stride(d), KP = glm_kp(d);
+    // padded records [a | 0 .. | y | 0 ..]; the tile past the data stays zero
+    std::vector<double> rec;
+    try {
+        rec.assign((size_t)glm_padded(m->m) * RS, 0.0);
+    } catch (const std::bad_alloc &) {
+        return fail(c, SVGD_ERR_RUNTIME, "[Runtime Error] Device GLM records: out of memory.");
+    }
+    for (int64_t j = 0; j < m->m; ++j) {
+        std::copy(m->A.data() + (size_t)j * d, m->A.data() + (size_t)(j + 1) * d, rec.data() + (size_t)j * RS);
+        rec[(size_t)j * RS + KP] = m->y[(size_t)j];
+    }
+    // data splits: the work-groups take equal time, so the grid (row groups x
+    // S) should fill the device's resident slots a whole number of times, at
+    // most twice (as ksd_alloc sizes its column splits); a launch uses
+    // min(smax, tiles of its window)
+    const int64_t groups = std::max<int64_t>(1, (c->nrows + GLM_ROWS_PER_WG - 1) / GLM_ROWS_PER_WG);
+    int cus = 0;
+    HIPCHK(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
+    const int64_t resident = (int64_t)std::max(1, cus) * glm_blocks_per_cu(d, m->link);
+    g.smax = (int)std::min<int64_t>(std::max<int64_t>(1, 2 * resident / groups), glm_tiles(m->m));
+    g.ldp = std::max<int64_t>(1, c->nrows);
+    CHK(dalloc(c, &g.rec, (int64_t)rec.size()));
+    CHK(dalloc(c, &g.part, (int64_t)g.smax * g.ldp * d));
+    HIPCHK(c, hipMemcpyAsync(g.rec, rec.data(), sizeof(double) * rec.size(), hipMemcpyHostToDevice,
+                             c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    g.link = m->link;
+    g.lik_scale = m->lik_scale;
+    g.prior_prec = m->prior_prec;
+    g.m0 = m->m0;
+    g.count = m->count;
+    g.m = m->m;
+    c->dm_k = 0; // the two device models exclude each other
+    return SVGD_OK;
+}
+
+int svgd_set_device_glm_batch(svgd_ctx *c, int64_t m0, int64_t count)
+{
+    if (!c) return SVGD_ERR_ARG;
+    if (c->glm.m == 0) return fail(c, SVGD_ERR_UNSET, "[Unset Error] No device GLM set.");
+    if (m0 < 0 || count < 1 || m0 > c->glm.m || count > c->glm.m - m0)
+        return fail(c, SVGD_ERR_ARG, "[Argument Error] Batch window outside the data.");
+    CHK(resolve_pending(c));
+    c->glm.m0 = m0;
+    c->glm.count = count;
     return SVGD_OK;
 }
 
@@ -2813,10 +2917,9 @@ int svgd_device_logp_grad(svgd_ctx *c, double *G_shard_out)
 {
     CHK(check_ready(c));
     CHK(resolve_pending(c));
-    if (c->dm_k == 0) return fail(c, SVGD_ERR_UNSET, "[Unset Error] No device model set.");
+    if (!has_device_model(c)) return fail(c, SVGD_ERR_UNSET, "[Unset Error] No device model set.");
     if (!G_shard_out) return fail(c, SVGD_ERR_ARG, "[Argument Error] Null output buffer.");
-    HIPCHK(c, launch_gauss_grad(c->X + (size_t)c->row0 * c->dim, c->nrows, c->dim, c->dm_k,
-                                c->dm_mu, c->dm_prec, c->phi, c->stream));
+    CHK(launch_device_model_grad(c, c->X + (size_t)c->row0 * c->dim, c->nrows, c->phi));
     HIPCHK(c, hipMemcpyAsync(G_shard_out, c->phi, sizeof(double) * (size_t)c->nrows * c->dim,
                              hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2871,7 +2974,7 @@ int svgd_ksd(svgd_ctx *c, const double *G_shard, double a, double *ksd2_v, doubl
     CHK(check_results(c));
     if (!std::isfinite(a) || !(a > 0.0))
         return fail(c, SVGD_ERR_ARG, "[Argument Error] The KSD kernel scale must be finite and positive.");
-    if (!G_shard && c->dm_k == 0)
+    if (!G_shard && !has_device_model(c))
         return fail(c, SVGD_ERR_ARG,
                     "[Argument Error] Null log-gradient buffer and no device model set.");
     CHK(resolve_pending(c));
@@ -2886,8 +2989,7 @@ int svgd_ksd(svgd_ctx *c, const double *G_shard, double a, double *ksd2_v, doubl
         if (c->nrows > 0)
             HIPCHK(c, hipMemcpyAsync(k.G + off, G_shard, bytes, hipMemcpyHostToDevice, c->stream));
     } else {
-        HIPCHK(c, launch_gauss_grad(c->X + off, c->nrows, d, c->dm_k, c->dm_mu, c->dm_prec, k.G + off,
-                                    c->stream));
+        CHK(launch_device_model_grad(c, c->X + off, c->nrows, k.G + off));
     }
     // the observer's collectives stay out of the step's collective hash and
     // of the level-2 diagnostic spans

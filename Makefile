@@ -9,7 +9,7 @@ SRC_DIR := svgdcpp_amd/csrc
 LIB := svgdcpp_amd/libsvgdcpp_amd.so
 OBJS := $(SRC_DIR)/svgd_kernels.o $(SRC_DIR)/svgd_collect.o $(SRC_DIR)/svgd_ksd.o $(SRC_DIR)/svgd_capi.o $(SRC_DIR)/plan.o $(SRC_DIR)/host_models.o \
         $(SRC_DIR)/hostcomm.o $(SRC_DIR)/svgd_glm.o $(SRC_DIR)/host_glm.o
-HDRS := $(SRC_DIR)/svgd_kernels.h $(SRC_DIR)/plan.h $(SRC_DIR)/svgd_ksd.h $(SRC_DIR)/svgd_device.h $(SRC_DIR)/svgd_exp_table.h \
+HDRS := $(SRC_DIR)/svgd_kernels.h $(SRC_DIR)/built.h $(SRC_DIR)/dispatch.h $(SRC_DIR)/plan.h $(SRC_DIR)/svgd_ksd.h $(SRC_DIR)/svgd_device.h $(SRC_DIR)/svgd_exp_table.h \
         $(SRC_DIR)/svgd_glm.h $(SRC_DIR)/host_glm.h include/svgdcpp_amd/svgd_capi.h
 
 all: $(LIB)
@@ -81,7 +81,7 @@ build/test_glm: tests/cpp/test_glm.cpp $(CPP_HDRS) $(LIB)
 # linked into a self-checking driver (the HIP host code needs a GPU: see
 # tests/cpp/sanitize_host.cpp).  Run by tests/test_sanitize.py.
 SAN := -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=all
-build/sanitize_host: tests/cpp/sanitize_host.cpp $(SRC_DIR)/plan.cpp $(SRC_DIR)/plan.h $(SRC_DIR)/host_models.cpp oracle/svgd_oracle.c
+build/sanitize_host: tests/cpp/sanitize_host.cpp $(SRC_DIR)/plan.cpp $(SRC_DIR)/plan.h $(SRC_DIR)/built.h $(SRC_DIR)/host_models.cpp oracle/svgd_oracle.c
 	@mkdir -p build/san
 	gcc -O1 -g -std=c11 -fopenmp -ffp-contract=off $(SAN) -c oracle/svgd_oracle.c -o build/san/oracle.o
 	$(CXX) -O1 -g -std=c++17 -fopenmp $(SAN) -c $(SRC_DIR)/plan.cpp -o build/san/plan.o

@@ -23,21 +23,6 @@
 
 namespace svgd_amd {
 
-bool pick_tiles(int d, int *KP, int *NCB)
-{
-    struct {
-        int maxd, kp, ncb;
-    } tab[] = {{4, 4, 1},   {8, 8, 1},   {12, 12, 1}, {15, 16, 1}, {16, 16, 2},
-               {31, 32, 2}, {32, 32, 3}, {63, 64, 4}, {64, 64, 5}};
-    for (auto &e : tab)
-        if (d <= e.maxd) {
-            *KP = e.kp;
-            *NCB = e.ncb;
-            return true;
-        }
-    return false;
-}
-
 // Which phi kernel a context runs, decided once (svgd_capi.cpp allocates for
 // it, run_phi launches it, svgd_phi_kernel_name prints it):
 //   fp64 d <= 16: the row stream, or the symmetric pass where it pays
@@ -68,10 +53,9 @@ bool plan_phi(int dim, int64_t n, int dtype, int plan_world, int64_t row0, const
     if (b3) p->b3_rg = k.phi_b3_rg.or_(1);
     if (rows) {
         p->R = phi_rows_per_lane(dim);
-        // 8-wave work-groups, 8192-entry table, columns split over the waves
-        // (kind 2); the 4-wave kernel (kind 0) serves the full-matrix scales
-        // (signature rows) and an R the 8-wave build does not have
-        p->rows_kind = cap.rows_t8k ? 2 : 0;
+        // 8-wave work-groups, 8192-entry table, columns split over the waves;
+        // the 4-wave kernel serves the full-matrix scales (matrix_scale_plan)
+        p->rows_kind = ROWS_8W;
         // symmetric phi pass: isotropic scales, d <= 8 (a pair feeds two
         // particles).  One rank: default since round 5 from N = 32768 up (with 16-byte record reads
         // cfg3 phi 3.59 -> 3.08 ms, step 4.12 -> 3.68 ms, cfg4 65.5 -> 56.5
@@ -110,14 +94,12 @@ void phi_plan_name(const PhiPlan &p, const PhiCaps &cap, char *buf, int len)
     case PHI_SYM:
         snprintf(buf, (size_t)len, "k_phi_sym<%d>", p.dim);
         break;
-    case PHI_ROWS:
-        // <D, R, NW, TABN, WC>.  Kind 2: T8K_NW waves, the 8192-entry table,
-        // T8K_WC column groups; kind 0: the template's defaults, 4 waves,
-        // EXP_TB = 4096 entries, 1.  These constants of svgd_kernels.hip have
-        // no accessor, so they are mirrored here.
-        snprintf(buf, (size_t)len, "k_phi_rows<%d, %d, %s>", p.dim, p.R,
-                 p.rows_kind == 2 ? "8, 8192, 8" : "4, 4096, 1");
+    case PHI_ROWS: {
+        // <D, R, NW, TABN, WC>, the geometry the launcher instantiates (built.h)
+        const RowsGeom g = rows_geom(p.rows_kind);
+        snprintf(buf, (size_t)len, "k_phi_rows<%d, %d, %d, %d, %d>", p.dim, p.R, g.NW, g.TABN, g.WC);
         break;
+    }
     case PHI_B3:
         snprintf(buf, (size_t)len, "k_phi_b3<%d, %d, %d, %s, %d>", p.KP, p.NCB, cap.b3_waves, tf[p.s1v],
                  p.b3_rg);

@@ -1,13 +1,15 @@
 // plan.h -- the tuning knobs and the phi plan (internal; host only, no HIP).
 //
-// svgd_capi.cpp reads the environment once into Knobs (read_knobs) and asks
-// the kernel translation unit what it has built (PhiCaps); plan_phi
+// svgd_capi.cpp reads the environment once into Knobs (read_knobs) and takes
+// what is built for the dimension from built.h (phi_caps); plan_phi
 // (plan.cpp) turns those into the one PhiPlan a context allocates for,
 // launches from and reports as its kernel name.
 #pragma once
 #include <stdint.h>
 
 #include <string>
+
+#include "built.h"
 
 namespace svgd_amd {
 
@@ -52,19 +54,6 @@ enum PhiPath {
     PHI_B3,       // k_phi_b3: fp32 products as bf16 part products
 };
 
-// What the launchers (svgd_kernels.h) answer for this dimension and dtype.
-struct PhiCaps {
-    int rows_kp;   // med_rec_stride(d) where the row stream has this d (d <= ROWS_MAX_D), else 0
-    bool rows_t8k; // phi_rows_t8k_supported(d, phi_rows_per_lane(d))
-    bool sym;      // phi_sym_supported(d)
-    bool tile_s1v; // phi_tile_s1v(d)
-    bool f32s, b3; // phi_f32s_supported / phi_b3_supported of pick_tiles' class
-    // template arguments only the kernel name needs
-    int tile_waves;   // phi_tile_cfg of the dtype: k_phi's waves per work-group ...
-    bool tile_pre;    // ... and its register prefetch
-    int b3_waves;     // k_phi_b3's waves: phi_b3_rows_per_wg(1) / 16
-};
-
 struct PhiPlan {
     PhiPath path = PHI_ROWS;
     int dim = 0;
@@ -72,23 +61,29 @@ struct PhiPlan {
     int NCB = 0;       // 16-column blocks of V (tile kernels)
     int VW = 0;        // 16 NCB
     bool s1v = false;  // d = 16 NCB: row sums on the VALU, no V column of ones
-    int R = 0;         // row stream: rows per lane
-    int rows_kind = 0; // row stream: 2 = 8 waves, 8192-entry table; 0 = 4 waves (the matrix scales' kernel)
+    int R = 0;         // row stream: phi_rows_per_lane(dim)
+    RowsKind rows_kind = ROWS_8W; // row stream: the geometry launched (ROWS_4W under a matrix scale)
     int b3_rg = 1;     // k_phi_b3's row groups per wave
     bool rows() const { return path == PHI_SYM || path == PHI_ROWS; }
     // the kernel's epilogue applies the optimizer update (else k_opt_update)
     bool fused() const { return rows() || path == PHI_F32S || path == PHI_B3; }
 };
 
-// (KP, NCB) tile class of dimension d; false above 64
-bool pick_tiles(int d, int *KP, int *NCB);
-// rows per lane of k_phi_rows (register budget)
-inline int phi_rows_per_lane(int d) { return d <= 8 ? 4 : 2; }
 // The phi plan of rows [row0, ...) of n particles shared by plan_world
 // ranks; false if the device path has no kernel for dim.  Pure: no HIP call,
 // no environment read, no context.
 bool plan_phi(int dim, int64_t n, int dtype, int plan_world, int64_t row0, const Knobs &k,
               const PhiCaps &cap, PhiPlan *p);
+
+// A full-matrix kernel scale is chosen after the plan was made and modifies
+// the launch per call: no symmetric pass, the 4-wave row kernel (signature
+// rows).  The tile paths launch the planned kernel on transformed operands.
+inline PhiPlan matrix_scale_plan(PhiPlan p)
+{
+    if (p.path == PHI_SYM) p.path = PHI_ROWS;
+    p.rows_kind = ROWS_4W;
+    return p;
+}
 
 // The plan's kernel with its template arguments, as rocprofv3 prints it
 // (svgd_phi_kernel_name): the only place that spells them.

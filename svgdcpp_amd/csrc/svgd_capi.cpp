@@ -775,22 +775,22 @@ int upload_state(svgd_ctx *c, int nsel, const uint64_t *ranks, uint64_t lo_key, 
 
 // One sweep over this rank's median pair tiles (mode 0 collect, 1 radix
 // histogram, 2 debug dump) on the row-stream (d <= 16) or MFMA tile kernel.
+// (the collect pass, mode 0, also histograms its candidates in key-range
+// buckets: c->bpart, which the other modes' launchers leave alone)
+PairArgs pair_args(svgd_ctx *c, uint64_t *regions, int64_t cap, double *dbg)
+{
+    return PairArgs{c->n,      c->pnb,   c->tile0, c->tile0 + c->own_tiles, regions, cap,
+                    c->counts, c->below, c->st,    c->ghist,                c->bpart, dbg};
+}
+
 hipError_t pair_pass(svgd_ctx *c, int mode, int grid, uint64_t *regions, int64_t cap, double *dbg)
 {
-    // the collect pass (mode 0) also histograms its candidates in key-range buckets
-    uint32_t *bp = mode == 0 ? c->bpart : nullptr;
+    const PairArgs a = pair_args(c, regions, cap, dbg);
     if (c->rowpath)
-        return launch_pair_rows(c->dim, c->plan.KP, mode, grid, c->xc, c->nrm, c->xf, nmax_cur(c), c->n,
-                                c->pnb, c->tile0,
-                                c->tile0 + c->own_tiles, regions, cap, c->counts, c->below, c->st,
-                                c->ghist, bp, dbg, c->stream);
+        return launch_pair_rows(c->dim, c->plan.KP, mode, grid, c->xc, c->nrm, c->xf, nmax_cur(c), a, c->stream);
     if (c->dtype == SVGD_F32)
-        return launch_pair_tiles_f32(c->plan.KP, mode, grid, c->xcf, c->nrmf, c->n, c->pnb, c->tile0,
-                                     c->tile0 + c->own_tiles, regions, cap, c->counts, c->below,
-                                     c->st, c->ghist, bp, dbg, c->XK, c->stream);
-    return launch_pair_tiles(c->plan.KP, mode, grid, c->xc, c->nrm, c->n, c->pnb, c->tile0,
-                             c->tile0 + c->own_tiles, regions, cap, c->counts, c->below, c->st,
-                             c->ghist, bp, dbg, c->stream);
+        return launch_pair_tiles<float>(c->plan.KP, mode, grid, c->xcf, c->nrmf, c->XK, a, c->stream);
+    return launch_pair_tiles<double>(c->plan.KP, mode, grid, c->xc, c->nrm, nullptr, a, c->stream);
 }
 
 constexpr double WIDE_SIGMA = 8.0; // re-bracket after a miss
@@ -1100,17 +1100,14 @@ int sample_bracket(svgd_ctx *c, bool preset)
 // host (ready at ev_cnt).
 int collect_counts(svgd_ctx *c)
 {
+    const PairArgs a = pair_args(c, c->regions, c->reg_cap, nullptr);
     if (c->rowpath && c->mcol && c->med_path != SVGD_MEDIAN_DIRECT && c->band_est <= MCOL_MAX_BAND)
         // bracket collect: fp32 MFMA classification, exact keys for the band
         // (a thin band only: each band pair is staged and finished one by one)
-        HIPCHK(c, launch_pair_mcol(c->dim, c->collect_grid, c->xc, c->xf, nmax_cur(c), c->n, c->pnb,
-                                   c->tile0, c->tile0 + c->own_tiles, c->regions, c->reg_cap,
-                                   c->counts, c->below, c->st, c->bpart, c->xsplit, c->stream));
+        HIPCHK(c, launch_pair_mcol(c->dim, c->collect_grid, c->xc, c->xf, nmax_cur(c), c->xsplit, a, c->stream));
     else if (!c->rowpath && c->dtype == SVGD_F32 && c->mcol)
         // fp32 tile path: k_pair_tiles' keys, rows held in VGPRs, no LDS
-        HIPCHK(c, launch_pair_tcol(c->plan.KP, c->collect_grid, c->xcf, c->nrmf, c->XK, c->n, c->pnb,
-                                   c->tile0, c->tile0 + c->own_tiles, c->regions, c->reg_cap,
-                                   c->counts, c->below, c->st, c->bpart, c->stream));
+        HIPCHK(c, launch_pair_tcol(c->plan.KP, c->collect_grid, c->xcf, c->nrmf, c->XK, a, c->stream));
     else
         HIPCHK(c, pair_pass(c, 0, c->collect_grid, c->regions, c->reg_cap, nullptr));
     HIPCHK(c, launch_counts_reduce(c->below, c->counts, c->nregions, c->reg_cap, c->st, c->bpart,
@@ -1415,12 +1412,12 @@ int run_phi(svgd_ctx *c, const OptArgs *opt)
     }
     if (med_end) diag_end(c, c->stream, med_end, DG_PHI_WAIT, true);
     // A matrix scale, chosen after the plan was made, modifies the planned
-    // launch per call: no symmetric pass, the 4-wave row kernel (kind 0:
-    // signature rows, sc_sgn), zc / zcf = L^T xc for xc / xcf, wv = 2 M xc.
-    const PhiPlan &p = c->plan;
+    // launch per call (matrix_scale_plan): no symmetric pass, the 4-wave row
+    // kernel (signature rows, sc_sgn), zc / zcf = L^T xc for xc / xcf, wv = 2 M xc.
     const bool mat = matrix_scale(c);
-    const PhiPath path = mat && p.path == PHI_SYM ? PHI_ROWS : p.path;
-    const int rows_kind = mat ? 0 : p.rows_kind;
+    const PhiPlan p = mat ? matrix_scale_plan(c->plan) : c->plan;
+    const PhiPath path = p.path;
+    const RowsKind rows_kind = p.rows_kind;
     if (mat) {
         // M = factor * src, L = chol(M), a_eff = 1 (GaussianRBFKernel.hpp:189-210)
         const double factor = c->scale_method == SVGD_SCALE_HESSIAN
@@ -1511,24 +1508,23 @@ int run_phi(svgd_ctx *c, const OptArgs *opt)
             o2.v += h * d;
             if (o2.bak) o2.bak += h * d;
             if (o2.xh) o2.xh += h * d;
-            HIPCHK(c, launch_phi_rows(c->dim, p.R, c->rec, c->scal, c->row0, h, c->n, c->S2, c->part, h,
-                                      inv_n, nullptr, nullptr, nmax_cur(c), c->phi, &o1, c->stream, k1,
-                                      rows_kind));
+            HIPCHK(c, launch_phi_rows(c->dim, rows_kind, c->rec, c->scal, c->row0, h, c->n, c->S2, c->part, h,
+                                      inv_n, nullptr, nullptr, nmax_cur(c), c->phi, &o1, c->stream, k1));
             HIPCHK(c, hipEventRecord(c->ev_xhalf, c->stream));
             hipEvent_t k2 = diag_begin(c, c->stream);
             hipEvent_t k3 = k2 ? take_ev(c) : nullptr;
-            HIPCHK(c, launch_phi_rows(c->dim, p.R, c->rec, c->scal, c->row0 + h, c->nrows - h, c->n, c->S2b,
+            HIPCHK(c, launch_phi_rows(c->dim, rows_kind, c->rec, c->scal, c->row0 + h, c->nrows - h, c->n, c->S2b,
                                       c->part, c->nrows - h, inv_n, nullptr, nullptr, nmax_cur(c),
-                                      c->phi + h * d, &o2, c->stream, k3, rows_kind));
+                                      c->phi + h * d, &o2, c->stream, k3));
             if (k2) c->ev_diag.push_back({k2, k3, DG_PHI_KERNEL, true});
         } else {
-            HIPCHK(c, launch_phi_rows(c->dim, p.R, c->rec, c->scal, c->row0, c->nrows, c->n, c->S, c->part,
+            HIPCHK(c, launch_phi_rows(c->dim, rows_kind, c->rec, c->scal, c->row0, c->nrows, c->n, c->S, c->part,
                                       c->ldp, inv_n, mat ? c->wv : nullptr, mat ? c->sc_sgn : nullptr,
-                                      mat ? nullptr : nmax_cur(c), c->phi, opt, c->stream, k1, rows_kind));
+                                      mat ? nullptr : nmax_cur(c), c->phi, opt, c->stream, k1));
         }
         break;
     case PHI_B3:
-        HIPCHK(c, launch_phi_b3(p.KP, p.NCB, c->B3, c->cvf, c->scal, c->row0, c->nrows, ntl, c->dim, inv_n,
+        HIPCHK(c, launch_phi_b3(p.KP, p.NCB, p.s1v, c->B3, c->cvf, c->scal, c->row0, c->nrows, ntl, c->dim, inv_n,
                                 mat ? c->wv : nullptr, c->xc, p.KP, c->phi, opt, p.b3_rg, c->stream));
         break;
     case PHI_F32S:
@@ -1537,15 +1533,17 @@ int run_phi(svgd_ctx *c, const OptArgs *opt)
                                   p.KP, c->phi, opt, c->stream));
         break;
     case PHI_TILE_F32:
-        HIPCHK(c, launch_phi_f32(p.KP, p.NCB, mat ? c->zcf : c->xcf, c->cvf, c->Vf, c->scal, c->row0,
-                                 c->nrows, (c->n + TB - 1) / TB, c->n, c->dim, inv_n,
-                                 mat ? c->wv : nullptr, c->xc, c->phi, c->stream));
+        HIPCHK(c, launch_phi<float>(p.KP, p.NCB, p.s1v, mat ? c->zcf : c->xcf, c->cvf, c->Vf, c->scal, c->row0,
+                                    c->nrows, (c->n + TB - 1) / TB, c->n, c->dim, inv_n,
+                                    mat ? c->wv : nullptr, c->xc, c->phi, c->stream));
         break;
-    case PHI_TILE_F64:
-        HIPCHK(c, launch_phi(p.KP, p.NCB, mat ? c->zc : c->xc, c->cvec, c->V, c->scal, c->row0,
-                             c->nrows, (c->n + TB - 1) / TB, c->n, c->dim, inv_n, mat ? c->wv : nullptr,
-                             c->phi, c->stream));
+    case PHI_TILE_F64: {
+        const double *x = mat ? c->zc : c->xc; // (the kernel's columns and its epilogue's rows)
+        HIPCHK(c, launch_phi<double>(p.KP, p.NCB, p.s1v, x, c->cvec, c->V, c->scal, c->row0, c->nrows,
+                                     (c->n + TB - 1) / TB, c->n, c->dim, inv_n, mat ? c->wv : nullptr, x,
+                                     c->phi, c->stream));
         break;
+    }
     }
     if (k0) {
         if (!c->rowpath) HIPCHK(c, hipEventRecord(k1, c->stream));
@@ -1884,17 +1882,9 @@ Knobs read_knobs()
     return k;
 }
 
-// What the kernel translation unit has built for (dim, dtype)
-PhiCaps phi_caps(int dim, int dtype)
-{
-    int KP = 0, NCB = 0, nw = 0, pre = 0;
-    (void)pick_tiles(dim, &KP, &NCB);
-    phi_tile_cfg(dtype != SVGD_F32, &nw, &pre);
-    return PhiCaps{dim >= 1 && dim <= ROWS_MAX_D ? med_rec_stride(dim) : 0,
-                   phi_rows_t8k_supported(dim, phi_rows_per_lane(dim)), phi_sym_supported(dim),
-                   phi_tile_s1v(dim), phi_f32s_supported(KP, NCB), phi_b3_supported(KP, NCB),
-                   nw, pre != 0, phi_b3_rows_per_wg(1) / 16};
-}
+// What the kernel translation unit has built for (dim, dtype): the lists of
+// built.h, with the wave counts of this build
+PhiCaps built_caps(int dim, int dtype) { return phi_caps(dim, dtype == SVGD_F32, phi_build()); }
 
 // Step 1: this rank's rows and its range of the median's pair tiles.
 void plan_rows_tiles(svgd_ctx *c, int sim_world)
@@ -1966,7 +1956,7 @@ int setup_sym(svgd_ctx *c, int ncu)
     // the row stream's hand-over inside k_phi_sym (symok = 0): its
     // 8-wave work-groups, one wave of them (<= c->S, the part buffer's splits)
     {
-        const int64_t rows_wg = phi_rows_t8k_rows(4);
+        const int64_t rows_wg = rows_geom(ROWS_8W).rows_per_wg(phi_rows_per_lane(dim));
         const int64_t ib = std::max<int64_t>(1, (c->nrows + rows_wg - 1) / rows_wg);
         c->sym_fS = (int)std::max<int64_t>(1, std::min<int64_t>(c->S, ncu / ib));
     }
@@ -2023,8 +2013,8 @@ int alloc_phi_rows(svgd_ctx *c)
     // block wave per slot left a tail of idle CUs (measured at cfg3, phi
     // launch: S x1 4.00 ms, x2 3.83-3.93, x4 3.81-3.90, x8 3.91-3.95 -- x2
     // and x4 tie, x2 has half the partials)
-    const int64_t resident = (int64_t)phi_rows_blocks_per_cu(dim, p.R, p.rows_kind) * ncu;
-    const int64_t rows_wg = p.rows_kind == 2 ? phi_rows_t8k_rows(p.R) : 256 * (int64_t)p.R;
+    const int64_t resident = (int64_t)phi_rows_blocks_per_cu(dim, p.rows_kind) * ncu;
+    const int64_t rows_wg = rows_geom(p.rows_kind).rows_per_wg(p.R);
     auto splits = [&](int64_t rows) {
         constexpr int split_mult = 2;
         const int64_t ib = std::max<int64_t>(1, (rows + rows_wg - 1) / rows_wg);
@@ -2215,7 +2205,7 @@ int init_ctx(svgd_ctx *c, int dim, int64_t n, int dtype, int device, int sim_wor
     c->dtype = dtype;
     c->device = device;
     plan_rows_tiles(c, sim_world);
-    if (!plan_phi(dim, n, dtype, c->plan_world, c->row0, c->knobs, phi_caps(dim, dtype), &c->plan))
+    if (!plan_phi(dim, n, dtype, c->plan_world, c->row0, c->knobs, built_caps(dim, dtype), &c->plan))
         return fail(c, SVGD_ERR_DIM, "[Dimension Error] Device path supports dimension <= 64.");
     c->rowpath = c->plan.rows();
     HIPCHK(c, hipSetDevice(device));
@@ -3174,11 +3164,12 @@ int svgd_get_timing(svgd_ctx *c, double *phi_ms, double *median_ms, int64_t *cou
 
 // (The plan is made at creation and a matrix scale is chosen afterwards, so
 // the name stays the isotropic-scale kernel's: under a matrix scale a row
-// stream or symmetric-pass context launches k_phi_rows<D, R, 4, 4096, 1>.)
+// stream or symmetric-pass context launches matrix_scale_plan's kernel, the
+// row stream in its 4-wave geometry.)
 int svgd_phi_kernel_name(const svgd_ctx *c, char *buf, int cap)
 {
     if (!c || !buf || cap <= 0) return SVGD_ERR_ARG;
-    phi_plan_name(c->plan, phi_caps(c->dim, c->dtype), buf, cap);
+    phi_plan_name(c->plan, built_caps(c->dim, c->dtype), buf, cap);
     return SVGD_OK;
 }
 
@@ -3190,7 +3181,7 @@ int svgd_plan_phi_name(int dim, int64_t n, int dtype, int world, int rank, char 
     int64_t row0 = 0, row1 = 0;
     svgd_plan_rows(n, world, rank, &row0, &row1);
     PhiPlan p;
-    const PhiCaps caps = phi_caps(dim, dtype);
+    const PhiCaps caps = built_caps(dim, dtype);
     if (!plan_phi(dim, n, dtype, world, row0, read_knobs(), caps, &p)) return SVGD_ERR_DIM;
     phi_plan_name(p, caps, buf, cap);
     return SVGD_OK;

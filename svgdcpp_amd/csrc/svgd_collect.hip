@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include <type_traits>
 
+#include "dispatch.h"
 #include "svgd_device.h"
 
 namespace svgd_amd {
@@ -1430,95 +1431,44 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) voi
 
 // ============================================================ launcher ==
 
-#define SVGD_TCOL_CASE(KPv)                                                                  \
-    case KPv:                                                                                \
-        hipLaunchKernelGGL((k_pair_tcol<KPv>), dim3(grid), dim3(256), 0, stream, xc, nrm, n, nb, \
-                           t0, t1, sc);                                                      \
-        break;
-#define SVGD_TCOL3_CASE(KPv)                                                                 \
-    case KPv:                                                                                \
-        hipLaunchKernelGGL((k_pair_tcol3<KPv>), dim3(grid), dim3(256), 0, stream, nrm, xk, n, nb, \
-                           t0, t1, sc);                                                      \
-        break;
-
 hipError_t launch_pair_tcol(int KP, int grid, const float *xc, const float *nrm, const uint32_t *xk,
-                            int64_t n, int64_t nb, int64_t t0, int64_t t1, uint64_t *regions,
-                            int64_t cap, uint32_t *counts, unsigned long long *below,
-                            const SelState *st, uint32_t *bpart, hipStream_t stream)
+                            const PairArgs &a, hipStream_t stream)
 {
-    if (grid <= 0 || t1 <= t0) return hipSuccess;
+    if (grid <= 0 || a.t1 <= a.t0) return hipSuccess;
     if (kb3_keys(KP) && !xk) return hipErrorInvalidValue;
-    SinkCollect sc{st, regions, cap, counts, below, nullptr, nullptr, bpart};
-    switch (KP) {
-        SVGD_TCOL_CASE(4)
-        SVGD_TCOL_CASE(8)
-        SVGD_TCOL_CASE(12)
-        SVGD_TCOL_CASE(16)
-        SVGD_TCOL3_CASE(32)
-        SVGD_TCOL3_CASE(64)
-    default:
-        return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    const SinkCollect sc = PairSinks(a, 0, nullptr, nullptr).sc;
+    const bool found = dispatch<PAIR_KP_F32>(KP, [&](auto kp) {
+        constexpr int K = decltype(kp)::value;
+        if constexpr (kb3_keys(K)) // the bf16 part-product keys
+            hipLaunchKernelGGL((k_pair_tcol3<K>), dim3(grid), dim3(256), 0, stream, nrm, xk, a.n, a.nb, a.t0,
+                               a.t1, sc);
+        else
+            hipLaunchKernelGGL((k_pair_tcol<K>), dim3(grid), dim3(256), 0, stream, xc, nrm, a.n, a.nb, a.t0,
+                               a.t1, sc);
+    });
+    return found ? hipGetLastError() : hipErrorInvalidValue;
 }
 
-#define SVGD_MCOL_CASE(Dv)                                                                   \
-    case Dv:                                                                                 \
-        hipLaunchKernelGGL((k_pair_mcol<Dv>), dim3(grid), dim3(256), 0, stream, xc, xf, xs, n, nb, \
-                           t0, t1, sc);                                                      \
-        break;
-#define SVGD_MCOLB_CASE(Dv)                                                                  \
-    case Dv:                                                                                 \
-        hipLaunchKernelGGL((k_pair_mcol<Dv, true>), dim3(grid), dim3(256), 0, stream, xc, xf, xs, n, \
-                           nb, t0, t1, sc);                                                  \
-        return hipGetLastError();
-
-
 hipError_t launch_pair_mcol(int d, int grid, const double *xc, const float *xf,
-                            const unsigned long long *nmax_bits, int64_t n, int64_t nb, int64_t t0,
-                            int64_t t1, uint64_t *regions, int64_t cap, uint32_t *counts,
-                            unsigned long long *below, const SelState *st, uint32_t *bpart,
-                            const uint32_t *xsplit, hipStream_t stream)
+                            const unsigned long long *nmax_bits, const uint32_t *xsplit,
+                            const PairArgs &a, hipStream_t stream)
 {
-    if (grid <= 0 || t1 <= t0) return hipSuccess;
+    if (grid <= 0 || a.t1 <= a.t0) return hipSuccess;
     if (!nmax_bits || !xf) return hipErrorInvalidValue;
-    SinkCollect sc{st, regions, cap, counts, below, xf, nmax_bits, bpart};
+    const SinkCollect sc = PairSinks(a, 0, xf, nmax_bits).sc;
     const uint4 *xs = reinterpret_cast<const uint4 *>(xsplit);
-    if (d <= 8 && xs) { // the bf16-split Gram (k_pair_mcol<D, true>)
-        switch (d) {
-            SVGD_MCOLB_CASE(1)
-            SVGD_MCOLB_CASE(2)
-            SVGD_MCOLB_CASE(3)
-            SVGD_MCOLB_CASE(4)
-            SVGD_MCOLB_CASE(5)
-            SVGD_MCOLB_CASE(6)
-            SVGD_MCOLB_CASE(7)
-            SVGD_MCOLB_CASE(8)
-        default:
-            break;
-        }
-    }
-    switch (d) {
-        SVGD_MCOL_CASE(1)
-        SVGD_MCOL_CASE(2)
-        SVGD_MCOL_CASE(3)
-        SVGD_MCOL_CASE(4)
-        SVGD_MCOL_CASE(5)
-        SVGD_MCOL_CASE(6)
-        SVGD_MCOL_CASE(7)
-        SVGD_MCOL_CASE(8)
-        SVGD_MCOL_CASE(9)
-        SVGD_MCOL_CASE(10)
-        SVGD_MCOL_CASE(11)
-        SVGD_MCOL_CASE(12)
-        SVGD_MCOL_CASE(13)
-        SVGD_MCOL_CASE(14)
-        SVGD_MCOL_CASE(15)
-        SVGD_MCOL_CASE(16)
-    default:
-        return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    const bool found = dispatch<ROW_DIMS>(d, [&](auto dc) {
+        constexpr int D = decltype(dc)::value;
+        if constexpr (D <= 8) // the bf16-split Gram is built for the dimensions that have the split
+            if (xs) {
+                hipLaunchKernelGGL((k_pair_mcol<D, true>), dim3(grid), dim3(256), 0, stream, xc, xf, xs, a.n,
+                                   a.nb, a.t0, a.t1, sc);
+                return;
+            }
+        hipLaunchKernelGGL((k_pair_mcol<D>), dim3(grid), dim3(256), 0, stream, xc, xf, xs, a.n, a.nb, a.t0,
+                           a.t1, sc);
+    });
+    return found ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 } // namespace svgd_amd

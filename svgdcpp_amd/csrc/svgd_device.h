@@ -162,4 +162,17 @@ struct SinkDebug {
     uint64_t *keys; // MODE 3: 64 x 64 keys of each sampled tile
 };
 
+// The sinks of one pair pass (host side: PairArgs, svgd_kernels.h).  The
+// bucket histograms belong to the collect (mode 0) alone.
+struct PairSinks {
+    SinkCollect sc;
+    SinkHist sh;
+    SinkDebug sd;
+    PairSinks(const PairArgs &a, int mode, const float *xf, const unsigned long long *nmax_bits)
+        : sc{a.st, a.regions, a.cap, a.counts, a.below, xf, nmax_bits, mode == 0 ? a.bpart : nullptr},
+          sh{a.st, a.ghist}, sd{a.dbg, a.n, a.sample}
+    {
+    }
+};
+
 } // namespace svgd_amd

@@ -25,6 +25,7 @@
 #include <stdint.h>
 
 #include "../../include/svgdcpp_amd/svgd_capi.h"
+#include "dispatch.h"
 #include "svgd_glm.h"
 
 namespace svgd_amd {
@@ -179,18 +180,14 @@ typedef void (*PassFn)(const double *, int, int64_t, const double *, int64_t, in
 
 PassFn pass_fn(int kp, int link)
 {
-#define SVGD_GLM_CASE(K)                                                                          \
-    case K:                                                                                       \
-        return link == SVGD_GLM_LOGISTIC ? &k_glm_pass<K, SVGD_GLM_LOGISTIC>                      \
-                                         : &k_glm_pass<K, SVGD_GLM_GAUSSIAN>;
-    switch (kp) {
-        SVGD_GLM_CASE(4) SVGD_GLM_CASE(8) SVGD_GLM_CASE(12) SVGD_GLM_CASE(16)
-        SVGD_GLM_CASE(20) SVGD_GLM_CASE(24) SVGD_GLM_CASE(28) SVGD_GLM_CASE(32)
-        SVGD_GLM_CASE(36) SVGD_GLM_CASE(40) SVGD_GLM_CASE(44) SVGD_GLM_CASE(48)
-        SVGD_GLM_CASE(52) SVGD_GLM_CASE(56) SVGD_GLM_CASE(60) SVGD_GLM_CASE(64)
-    }
-#undef SVGD_GLM_CASE
-    return nullptr;
+    // KP = 4, 8, .., 64
+    PassFn f = nullptr;
+    if (kp % 4 == 0)
+        dispatch_range<1, 16>(kp / 4, [&](auto q) {
+            constexpr int K = 4 * decltype(q)::value;
+            f = link == SVGD_GLM_LOGISTIC ? &k_glm_pass<K, SVGD_GLM_LOGISTIC> : &k_glm_pass<K, SVGD_GLM_GAUSSIAN>;
+        });
+    return f;
 }
 
 } // namespace glm

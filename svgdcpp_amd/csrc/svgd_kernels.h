@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "built.h"
+
 namespace svgd_amd {
 
 constexpr int RADIX_BITS = 11;
@@ -67,29 +69,25 @@ hipError_t launch_mean_center(const double *X, int64_t n, int d, int KP, int64_t
 hipError_t launch_prep_v(const double *xc, const double *G, const double *nrm, const double *a_ptr,
                          int64_t n, int64_t np, int d, int KP, int VW, double *V, double *cvec,
                          hipStream_t stream);
-// n: particles (columns j >= n are padding); an fp64 tile with d = 16 NCB
-// (phi_tile_s1v) sums P's rows on the VALU instead of a V column of ones
-hipError_t launch_phi(int KP, int NCB, const double *xc, const double *cvec, const double *V,
+// The tile phi k_phi<T, KP, NCB, ...> of a class in TILES_F64 / TILES_F32, or,
+// s1v (the plan's: d = 16 NCB), TILES_S1V: P's rows are summed on the VALU
+// instead of a V column of ones.  T = double, or float (SVGD_F32: fp32
+// operands xg, cvec, V; phi and the epilogue, from the fp64 xc, stay fp64).
+// n: particles (columns j >= n are padding)
+template <class T>
+hipError_t launch_phi(int KP, int NCB, bool s1v, const T *xg, const T *cvec, const T *V,
                       const double *a_ptr, int64_t row0, int64_t nrows, int64_t ntiles_j, int64_t n,
-                      int d, double inv_n, const double *wv, double *phi, hipStream_t stream);
-bool phi_tile_s1v(int d);
-void phi_tile_cfg(bool f64, int *nw, int *pre); // k_phi's waves per block and prefetch flag
-// fp32 variants of the tile kernels (SVGD_F32); phi and the epilogue stay fp64
-hipError_t launch_phi_f32(int KP, int NCB, const float *xg, const float *cvec, const float *V,
-                          const double *a_ptr, int64_t row0, int64_t nrows, int64_t ntiles_j,
-                          int64_t n, int d, double inv_n, const double *wv, const double *xc,
-                          double *phi, hipStream_t stream);
-hipError_t launch_pair_tiles_f32(int KP, int mode, int grid, const float *xc, const float *nrm,
-                                 int64_t n, int64_t nb, int64_t t0, int64_t t1, uint64_t *regions,
-                                 int64_t cap, uint32_t *counts, unsigned long long *below,
-                                 const SelState *st, unsigned long long *ghist, uint32_t *bpart,
-                                 double *dbg_out, const uint32_t *xk, hipStream_t stream);
+                      int d, double inv_n, const double *wv, const double *xc, double *phi,
+                      hipStream_t stream);
+// the wave counts and prefetch flag this translation unit was built with
+PhiBuild phi_build();
 hipError_t launch_cvt_f32(const double *src, int64_t cnt, float *dst, hipStream_t stream);
 // fp32 copy of the norms with +inf in the padding rows [n, np)
 hipError_t launch_cvt_nrm_f32(const double *src, int64_t n, int64_t np, float *dst, hipStream_t stream);
 // Sampled median keys on the tile path: ntiles random (block, block) pairs of
 // distinct full 64-particle blocks, all 64 x 64 keys each (xcf/nrmf: fp32 path)
 // xk: the F32 key parts when KP is 32 or 64 (launch_swz_keys_b3), else null
+// (mode 3 of launch_pair_tiles over a.t1 = ntiles tiles, a.sample = the keys)
 hipError_t launch_sample_tiles(int KP, const double *xc, const double *nrm, const float *xcf,
                                const float *nrmf, const uint32_t *xk, int64_t n, int64_t ntiles,
                                uint64_t *keys, hipStream_t stream);
@@ -111,15 +109,30 @@ struct OptArgs {
     double *xh = nullptr;        // X_{t+1} also stored here when set (pinned host mirror)
 };
 hipError_t launch_opt_update(const OptArgs &o, const double *g, hipStream_t stream);
+// One sweep over a rank's median pair tiles [t0, t1) of the nb x nb block
+// plan: what every pair pass takes besides its operands.
 // mode 0: collect keys in [st->lo_key, st->hi_key) into per-block regions and count
 // keys below lo_key; mode 1: radix histogram pass over all pairs (fallback);
-// mode 2: debug dump of every key in (i<j) row-major order.
-// bpart (mode 0, optional): per-block key-range bucket histograms [grid][NBK]
-hipError_t launch_pair_tiles(int KP, int mode, int grid, const double *xc, const double *nrm,
-                             int64_t n, int64_t nb, int64_t t0, int64_t t1, uint64_t *regions,
-                             int64_t cap, uint32_t *counts, unsigned long long *below,
-                             const SelState *st, unsigned long long *ghist, uint32_t *bpart,
-                             double *dbg_out, hipStream_t stream);
+// mode 2: debug dump of every key in (i<j) row-major order; mode 3 (tiles
+// only): every key of t1 sampled tiles.
+struct PairArgs {
+    int64_t n, nb, t0, t1;
+    uint64_t *regions; // mode 0: the collected keys, cap per work-group ...
+    int64_t cap;
+    uint32_t *counts;          // ... their counts ...
+    unsigned long long *below; // ... and the keys below the bracket
+    const SelState *st;
+    unsigned long long *ghist; // mode 1
+    uint32_t *bpart;           // mode 0, optional: per-block key-range bucket histograms [grid][NBK]
+    double *dbg;               // mode 2
+    uint64_t *sample = nullptr; // mode 3
+};
+// The MFMA tile pass k_pair_tiles<T, KP, mode>, KP in PAIR_KP_F64 (T = double)
+// or PAIR_KP_F32 (float: fp32 keys on the matrix cores; xk: the key parts at KP
+// 32 / 64, bf16 part-product keys, else unused)
+template <class T>
+hipError_t launch_pair_tiles(int KP, int mode, int grid, const T *xc, const T *nrm, const uint32_t *xk,
+                             const PairArgs &a, hipStream_t stream);
 // xf != nullptr (d <= 16): keys from the fp32 records (a bracket estimate only).
 // Sample pairs g0 .. g0+S-1 of the counter-based sequence -> keys[0 .. S-1]
 // (ranks draw disjoint index ranges of one sequence).
@@ -205,24 +218,20 @@ hipError_t launch_plan_select(const unsigned long long *cnt, SelState *st, int n
 constexpr int CAPR_MIN = 4096;
 
 // Row-stream path (d <= 16): particle records rec_j = [xc_j | G_j - 2a xc_j | c_j | 0..],
-// stride phi_rec_stride(d).  phi partials over S column splits -> part[S][ldp][d+1].
-constexpr int ROWS_MAX_D = 16;
-// record strides (doubles) of the row-stream path: phi records
-// [xc | G - 2a xc | c | 0..] and median records [xc | |xc|^2 | 0..]
-constexpr int phi_rec_stride(int d) { return ((2 * d + 1 + 7) / 8) * 8; }
-constexpr int med_rec_stride(int d) { return ((d + 1 + 3) / 4) * 4; }
-constexpr int med_f32_stride(int d) { return ((d + 1 + 7) / 8) * 8; }
+// stride phi_rec_stride(d) (built.h).  phi partials over S column splits ->
+// part[S][ldp][d+1].
 hipError_t launch_prep_rec(const double *xc, const double *G, const double *nrm,
                            const double *a_ptr, int64_t n, int64_t np, int d, int KP, int RS,
                            double *rec, hipStream_t stream);
-// opt (optional): the optimizer step applied to each phi element as the
-// reduce writes it (the step path: one launch fewer than launch_opt_update).
+// k_phi_rows<d, phi_rows_per_lane(d)> in the geometry rows_geom(kind), then
+// its reduce.  opt (optional): the optimizer step applied to each phi element
+// as the reduce writes it (the step path: one launch fewer than launch_opt_update).
 // ev_mid (optional): recorded between k_phi_rows and its reduce (diagnostics).
-hipError_t launch_phi_rows(int d, int R, const double *rec, const double *a_ptr,
+hipError_t launch_phi_rows(int d, RowsKind kind, const double *rec, const double *a_ptr,
                            int64_t row0, int64_t nrows, int64_t n, int S, double *part,
                            int64_t ldp, double inv_n, const double *wv, const double *sgn,
                            const unsigned long long *nmax_bits, double *phi, const OptArgs *opt,
-                           hipStream_t stream, hipEvent_t ev_mid = nullptr, int kind = 0,
+                           hipStream_t stream, hipEvent_t ev_mid = nullptr,
                            const int *skip = nullptr, bool reduce = true);
 // skip (optional): the reduce does nothing while *skip != 0.  reduce = false:
 // the row kernel alone
@@ -277,15 +286,11 @@ hipError_t launch_fill_tab8k(double *tab, hipStream_t stream);
 // or from the row stream's partials when symok = 0.  world = 1: own alone.
 hipError_t launch_sym_apply(const SymArgs &a, const double *own, const double *recv, const int64_t *xtab,
                             int world, int rank, const OptArgs *opt, hipStream_t stream);
-bool phi_sym_supported(int d);
-bool phi_sym_geom(int d, int *B, int *SRS, int *NSUB);
+bool phi_sym_geom(int d, int *B, int *SRS, int *NSUB); // false: d not in SYM_DIMS
 int phi_sym_blocks_per_cu(int d);
 // record prep + k_phi_sym (ev_k0 / ev_k1 around the pair kernel, optional)
 hipError_t launch_phi_sym(const SymArgs &a, hipEvent_t ev_k0, hipEvent_t ev_k1, hipStream_t stream);
 hipError_t launch_sym_finish(const SymArgs &a, const OptArgs *opt, hipStream_t stream);
-// kind 2: k_phi_rows with 8-wave work-groups and the mask-free 8192-entry exp table
-bool phi_rows_t8k_supported(int d, int R);
-int phi_rows_t8k_rows(int R); // rows per work-group of kind 2
 // full-matrix kernel scale: M = factor * sym(src) = L diag(sgn) L^T (Cholesky,
 // or an eigendecomposition when M is indefinite and d <= ROWS_MAX_D);
 // err = 0 positive definite, 2 indefinite, 1 non-finite / no convergence.
@@ -298,58 +303,50 @@ hipError_t launch_prep_rec_mat(const double *xc, const double *G, const double *
 hipError_t launch_prep_v_mat(const double *xc, const double *G, const double *M, const double *L,
                              int64_t n, int64_t np, int d, int KP, int VW, double *zc, double *V,
                              double *cvec, double *wv, hipStream_t stream);
+// The row-stream pair pass k_pair_rows<d, mode> (d in ROW_DIMS, modes 0..2);
 // mode 0 (collect) needs nmax_bits from launch_mean_center (classification margin).
+// xf != nullptr: the fp32 records (mode 0's classification)
 hipError_t launch_pair_rows(int d, int KP, int mode, int grid, const double *xc, const double *nrm,
-                            const float *xf, const unsigned long long *nmax_bits,
-                            int64_t n, int64_t nb, int64_t t0, int64_t t1, uint64_t *regions,
-                            int64_t cap, uint32_t *counts, unsigned long long *below,
-                            const SelState *st, unsigned long long *ghist, uint32_t *bpart,
-                            double *dbg_out, hipStream_t stream);
+                            const float *xf, const unsigned long long *nmax_bits, const PairArgs &a,
+                            hipStream_t stream);
 // Bracket collect (mode 0 of launch_pair_rows) with fp32 MFMA classification and
 // exact fp64 keys for the undecided band (d <= 16); same plan, outputs and keys.
-hipError_t launch_pair_mcol(int d, int grid, const double *xc, const float *xf,
-                            const unsigned long long *nmax_bits, int64_t n, int64_t nb, int64_t t0,
-                            int64_t t1, uint64_t *regions, int64_t cap, uint32_t *counts,
-                            unsigned long long *below, const SelState *st, uint32_t *bpart,
-                            const uint32_t *xsplit, hipStream_t stream);
 // (xsplit, d <= 8: the centring's split-bf16 operands -> the bf16-split Gram;
 // nullptr: the f32 Gram)
+hipError_t launch_pair_mcol(int d, int grid, const double *xc, const float *xf,
+                            const unsigned long long *nmax_bits, const uint32_t *xsplit,
+                            const PairArgs &a, hipStream_t stream);
 // fp32 tile-path collect (k_pair_tiles<float> MODE 0 on the matrix cores,
-// same keys): one region per block; KP in {4, 8, 12, 16, 32, 64}; xk: the
-// key parts at KP 32 / 64 (bf16 part-product keys), else unused
+// same keys): one region per block; KP in PAIR_KP_F32; xk: the key parts at
+// KP 32 / 64 (bf16 part-product keys), else unused
 hipError_t launch_pair_tcol(int KP, int grid, const float *xc, const float *nrm, const uint32_t *xk,
-                            int64_t n, int64_t nb, int64_t t0, int64_t t1, uint64_t *regions,
-                            int64_t cap, uint32_t *counts, unsigned long long *below,
-                            const SelState *st, uint32_t *bpart, hipStream_t stream);
+                            const PairArgs &a, hipStream_t stream);
 // F32 tile phi, streamed (k_phi_f32s): operand-ordered fp32 copies of the
 // columns (XS, VS: ntiles = ceil(n / 32) tiles of 32 particles; XS holds
 // ntiles * 32 * KP floats, VS ntiles * 2 * (VW/16 + 1) * 256) made by
 // launch_swz_f32 from the fp64 coordinates x (stride KP), V (stride VW) and
 // cvec; rows from the row-major fp32 copy xrow (stride KP) and crow.
-// KP % 16 == 0 (phi_f32s_supported); row0 % 16 == 0.
+// (KP, NCB) in TILES_F32S; row0 % 16 == 0.
 hipError_t launch_swz_f32(const double *x, int KP, const double *V, int VW, const double *cvec,
                           int64_t ntiles, float *XS, float *VS, hipStream_t stream);
-bool phi_f32s_supported(int KP, int NCB);
 // F32 tile phi on the bf16 matrix cores (k_phi_b3: each fp32 operand as three
 // bf16 parts, six part products per fp32 product): per 32-column tile
 // phi_b3_tile_words(KP, NCB) dwords of operand-ordered parts made by
 // launch_swz_b3 from x (stride KP), V (stride VW = 16 NCB) and cvec.
-// KP = 32 or 64; row0 % 16 == 0.
-bool phi_b3_supported(int KP, int NCB);
+// (KP, NCB) in TILES_B3, or, s1v (the plan's), TILES_S1V; rg in B3_RG: row
+// groups of 16 per wave; row0 % 16 == 0.
 int64_t phi_b3_tile_words(int KP, int NCB);
 hipError_t launch_swz_b3(const double *x, int KP, const double *V, int VW, const double *cvec,
                          int64_t n, int64_t ntiles, uint32_t *B3, hipStream_t stream);
-hipError_t launch_phi_b3(int KP, int NCB, const uint32_t *B3, const float *crow,
+hipError_t launch_phi_b3(int KP, int NCB, bool s1v, const uint32_t *B3, const float *crow,
                          const double *a_ptr, int64_t row0, int64_t nrows, int64_t ntiles, int d,
                          double inv_n, const double *wv, const double *xc, int xc_stride,
                          double *phi, const OptArgs *opt, int rg, hipStream_t stream);
-// rows per work-group of k_phi_b3 with rg row groups of 16 per wave (1 or 2)
-int phi_b3_rows_per_wg(int rg);
 hipError_t launch_phi_f32s(int KP, int NCB, const float *XS, const float *VS, const float *xrow,
                            const float *crow, const double *a_ptr, int64_t row0, int64_t nrows,
                            int64_t ntiles, int d, double inv_n, const double *wv, const double *xc,
                            int xc_stride, double *phi, const OptArgs *opt, hipStream_t stream);
-int phi_rows_blocks_per_cu(int d, int R, int kind = 0);
+int phi_rows_blocks_per_cu(int d, RowsKind kind);
 // G = grad log p of the Gaussian-sum model for `rows` particle rows (d <= 64)
 hipError_t launch_gauss_grad(const double *X, int64_t rows, int d, int k, const double *mu,
                              const double *prec, double *G, hipStream_t stream);

@@ -4376,56 +4376,37 @@ __global__ __launch_bounds__(256) void k_gauss_grad(const double *__restrict__ X
 
 // ============================================================ launchers ==
 
-#define SVGD_ROWS_CASE(Dv)                                                                   \
-    case Dv:                                                                                 \
-        if (kind == 0 && R == 1)                                                             \
-            hipLaunchKernelGGL((k_phi_rows<Dv, 1>), dim3(grid), dim3(256), 0, stream,   \
-                               rec, a_ptr, row0, nrows, n, S, part, ldp, sgn, nmax);               \
-        else if (kind == 0 && R == 2)                                                        \
-            hipLaunchKernelGGL((k_phi_rows<Dv, 2>), dim3(grid), dim3(256), 0, stream,   \
-                               rec, a_ptr, row0, nrows, n, S, part, ldp, sgn, nmax);               \
-        else if (kind == 0)                                                                  \
-            hipLaunchKernelGGL((k_phi_rows<Dv, 4>), dim3(grid), dim3(256), 0, stream,   \
-                               rec, a_ptr, row0, nrows, n, S, part, ldp, sgn, nmax);               \
-        else if (kind == 10)                                                                 \
-            hipLaunchKernelGGL((k_pair_rows<Dv, 0>), dim3(grid), dim3(256), 0, stream, xc, KP, \
-                               nrm, n, nb, t0, t1, sc, sh, sd);                              \
-        else if (kind == 11)                                                                 \
-            hipLaunchKernelGGL((k_pair_rows<Dv, 1>), dim3(grid), dim3(256), 0, stream, xc, KP, \
-                               nrm, n, nb, t0, t1, sc, sh, sd);                              \
-        else                                                                                 \
-            hipLaunchKernelGGL((k_pair_rows<Dv, 2>), dim3(grid), dim3(256), 0, stream, xc, KP, \
-                               nrm, n, nb, t0, t1, sc, sh, sd);                              \
-        break;
+// Every switch over a dimension, a tile class or a mode below is a dispatch()
+// over a list of built.h: the kernels named in its lambda are built for that
+// list and nothing else, and a value outside it is hipErrorInvalidValue.
+} // namespace svgd_amd
+#include "dispatch.h"
+namespace svgd_amd {
 
-static hipError_t launch_rows_kernel(int kind, int D, int R, int grid, const double *rec,
-                                     const double *a_ptr, int64_t row0, int64_t nrows, int64_t n,
-                                     int S, double *part, int64_t ldp, const double *sgn,
-                                     const unsigned long long *nmax, const double *xc, int KP,
-                                     const double *nrm, int64_t nb, int64_t t0, int64_t t1,
-                                     SinkCollect sc, SinkHist sh, SinkDebug sd, hipStream_t stream)
+static hipError_t launched(bool found) { return found ? hipGetLastError() : hipErrorInvalidValue; }
+
+// the row stream's geometries (built.h) are the kernel's: the 8-wave one the
+// T8K constants above, the 4-wave one k_phi_rows' template defaults
+template <int D, RowsKind K> struct RowsKernel {
+    static constexpr RowsGeom G = rows_geom(K);
+    static constexpr int R = phi_rows_per_lane(D);
+    static constexpr auto fn = k_phi_rows<D, R, G.NW, G.TABN, G.WC>;
+};
+static_assert(rows_geom(ROWS_8W).NW == T8K_NW && rows_geom(ROWS_8W).WC == T8K_WC &&
+                  rows_geom(ROWS_4W).TABN == EXP_TB && ROWS_MAX_D == 16,
+              "built.h restates the row stream's geometry");
+
+// f(kernel, threads per work-group) for k_phi_rows<d, R(d)> of the geometry
+template <class F> static bool with_rows_kernel(int d, RowsKind kind, F &&f)
 {
-    switch (D) {
-        SVGD_ROWS_CASE(1)
-        SVGD_ROWS_CASE(2)
-        SVGD_ROWS_CASE(3)
-        SVGD_ROWS_CASE(4)
-        SVGD_ROWS_CASE(5)
-        SVGD_ROWS_CASE(6)
-        SVGD_ROWS_CASE(7)
-        SVGD_ROWS_CASE(8)
-        SVGD_ROWS_CASE(9)
-        SVGD_ROWS_CASE(10)
-        SVGD_ROWS_CASE(11)
-        SVGD_ROWS_CASE(12)
-        SVGD_ROWS_CASE(13)
-        SVGD_ROWS_CASE(14)
-        SVGD_ROWS_CASE(15)
-        SVGD_ROWS_CASE(16)
-    default:
-        return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch<ROW_DIMS>(d, [&](auto dc) {
+        using K8 = RowsKernel<decltype(dc)::value, ROWS_8W>;
+        using K4 = RowsKernel<decltype(dc)::value, ROWS_4W>;
+        if (kind == ROWS_8W)
+            f(K8::fn, K8::G.NW * 64);
+        else
+            f(K4::fn, K4::G.NW * 64);
+    });
 }
 
 hipError_t launch_prep_rec(const double *xc, const double *G, const double *nrm,
@@ -4439,54 +4420,26 @@ hipError_t launch_prep_rec(const double *xc, const double *G, const double *nrm,
     return hipGetLastError();
 }
 
-// kind 2: k_phi_rows with 8 waves, the 8192-entry table and the columns split
-// over the 8 waves (WC = 8: one 64 R-row group per work-group); R = 4 for
-// d <= 8, 2 above (the register budget)
-bool phi_rows_t8k_supported(int d, int R) { return d >= 1 && d <= 16 && R == (d <= 8 ? 4 : 2); }
-int phi_rows_t8k_rows(int R) { return (T8K_NW / T8K_WC) * 64 * R; }
-#define SVGD_T8K_KERNEL(Dv) k_phi_rows<Dv, ((Dv) <= 8 ? 4 : 2), T8K_NW, 8192, T8K_WC>
-#define SVGD_T8K_CASE(Dv)                                                                       \
-    case Dv:                                                                                    \
-        hipLaunchKernelGGL((SVGD_T8K_KERNEL(Dv)), dim3(grid), dim3(T8K_NW * 64), 0, stream, rec, \
-                           a_ptr, row0, nrows, n, S, part, ldp, sgn, nmax);                     \
-        break;
-static hipError_t launch_rows_t8k(int d, int grid, const double *rec, const double *a_ptr,
-                                  int64_t row0, int64_t nrows, int64_t n, int S, double *part,
-                                  int64_t ldp, const double *sgn, const unsigned long long *nmax,
-                                  hipStream_t stream)
-{
-    switch (d) {
-        SVGD_T8K_CASE(1) SVGD_T8K_CASE(2) SVGD_T8K_CASE(3) SVGD_T8K_CASE(4)
-        SVGD_T8K_CASE(5) SVGD_T8K_CASE(6) SVGD_T8K_CASE(7) SVGD_T8K_CASE(8)
-        SVGD_T8K_CASE(9) SVGD_T8K_CASE(10) SVGD_T8K_CASE(11) SVGD_T8K_CASE(12)
-        SVGD_T8K_CASE(13) SVGD_T8K_CASE(14) SVGD_T8K_CASE(15) SVGD_T8K_CASE(16)
-    default:
-        return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-
-hipError_t launch_phi_rows(int d, int R, const double *rec, const double *a_ptr,
+hipError_t launch_phi_rows(int d, RowsKind kind, const double *rec, const double *a_ptr,
                            int64_t row0, int64_t nrows, int64_t n, int S, double *part,
                            int64_t ldp, double inv_n, const double *wv, const double *sgn,
                            const unsigned long long *nmax_bits, double *phi, const OptArgs *opt,
-                           hipStream_t stream, hipEvent_t ev_mid, int kind, const int *skip, bool reduce)
+                           hipStream_t stream, hipEvent_t ev_mid, const int *skip, bool reduce)
 {
     if (nrows <= 0) {
         if (ev_mid) return hipEventRecord(ev_mid, stream);
         return hipSuccess;
     }
-    const int rows_wg = kind == 2 ? phi_rows_t8k_rows(R) : 256 * R;
+    const int rows_wg = rows_geom(kind).rows_per_wg(phi_rows_per_lane(d));
     const int grid = (int)(((nrows + rows_wg - 1) / rows_wg) * S);
-    hipError_t e = kind == 2 ? launch_rows_t8k(d, grid, rec, a_ptr, row0, nrows, n, S, part, ldp, sgn,
-                                               nmax_bits, stream)
-                             : launch_rows_kernel(0, d, R, grid, rec, a_ptr, row0, nrows, n, S, part, ldp, sgn,
-                                      nmax_bits, nullptr, 0, nullptr, 0, 0, 0, SinkCollect{}, SinkHist{},
-                                      SinkDebug{}, stream);
+    hipError_t e = launched(with_rows_kernel(d, kind, [&](auto kernel, int threads) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), 0, stream, rec, a_ptr, row0, nrows, n, S,
+                           part, ldp, sgn, nmax_bits);
+    }));
     if (e != hipSuccess) return e;
     if (ev_mid && (e = hipEventRecord(ev_mid, stream)) != hipSuccess) return e;
     if (!reduce) return hipSuccess;
-    if (d > 16) return hipErrorInvalidValue; // k_phi_reduce's LDS holds d + 1 <= 17
+    // (d <= ROWS_MAX_D: k_phi_reduce's LDS holds d + 1 <= 17)
     const int64_t g = (nrows + phi_red_rows(d) - 1) / phi_red_rows(d);
     hipLaunchKernelGGL(k_phi_reduce, dim3(g), dim3(256), 0, stream, part, rec, a_ptr, row0, nrows,
                        d, phi_rec_stride(d), S, ldp, inv_n, wv, phi, opt ? *opt : OptArgs{},
@@ -4495,170 +4448,93 @@ hipError_t launch_phi_rows(int d, int R, const double *rec, const double *a_ptr,
 }
 
 hipError_t launch_pair_rows(int d, int KP, int mode, int grid, const double *xc, const double *nrm,
-                            const float *xf, const unsigned long long *nmax_bits,
-                            int64_t n, int64_t nb, int64_t t0, int64_t t1, uint64_t *regions,
-                            int64_t cap, uint32_t *counts, unsigned long long *below,
-                            const SelState *st, unsigned long long *ghist, uint32_t *bpart,
-                            double *dbg_out, hipStream_t stream)
+                            const float *xf, const unsigned long long *nmax_bits, const PairArgs &a,
+                            hipStream_t stream)
 {
-    if (grid <= 0 || t1 <= t0) return hipSuccess;
+    if (grid <= 0 || a.t1 <= a.t0) return hipSuccess;
     if (mode == 0 && !nmax_bits) return hipErrorInvalidValue;
-    SinkCollect sc{st, regions, cap, counts, below, xf, nmax_bits, mode == 0 ? bpart : nullptr};
-    SinkHist sh{st, ghist};
-    SinkDebug sd{dbg_out, n};
-    return launch_rows_kernel(10 + mode, d, 1, grid, nullptr, nullptr, 0, 0, n, 1, nullptr, 0, nullptr, nullptr, xc,
-                              KP, nrm, nb, t0, t1, sc, sh, sd, stream);
+    const PairSinks s(a, mode, xf, nmax_bits);
+    return launched(dispatch<ROW_DIMS>(d, [&](auto dc) {
+        return dispatch<PAIR_ROW_MODES>(mode, [&](auto mc) {
+            hipLaunchKernelGGL((k_pair_rows<decltype(dc)::value, decltype(mc)::value>), dim3(grid), dim3(256),
+                               0, stream, xc, KP, nrm, a.n, a.nb, a.t0, a.t1, s.sc, s.sh, s.sd);
+        });
+    }));
 }
 
 // fp64: 8-wave blocks, 2 per CU (76 KB LDS at d = 64), column tile prefetched
 // into registers; fp32 (small-N fallback of SVGD_F32): 4 waves, synchronous
 // staging.  SVGD_PHI_NW / _PRE / _WPE override at build time for measurements.
 #ifndef SVGD_PHI_NW
-#define SVGD_PHI_NW 8
+#define SVGD_PHI_NW PhiBuild{}.tile_nw
 #endif
 #ifndef SVGD_PHI_PRE
-#define SVGD_PHI_PRE 1
+#define SVGD_PHI_PRE PhiBuild{}.tile_pre
 #endif
+#ifndef SVGD_B3_NW
+#define SVGD_B3_NW PhiBuild{}.b3_nw
+#endif
+PhiBuild phi_build() { return PhiBuild{SVGD_PHI_NW, SVGD_PHI_PRE, SVGD_B3_NW}; }
 template <class T> struct PhiCfg {
-    static constexpr int NW = 4;
-    static constexpr bool PRE = false;
+    static constexpr int NW = TILE_F32_NW;
+    static constexpr bool PRE = TILE_F32_PRE;
 };
 template <> struct PhiCfg<double> {
     static constexpr int NW = SVGD_PHI_NW;
     static constexpr bool PRE = SVGD_PHI_PRE;
 };
 
-template <class T, int KPv, int NCBv, bool S1V>
-static hipError_t launch_phi_tile(const T *xg, const T *cvec, const T *V, const double *a_ptr,
-                                  int64_t row0, int64_t nrows, int64_t ntiles_j, int64_t n, int d,
-                                  double inv_n, const double *wv, const double *xc, double *phi,
-                                  hipStream_t stream)
-{
-    constexpr int NW = PhiCfg<T>::NW;
-    const int64_t grid = (nrows + 16 * NW - 1) / (16 * NW);
-    hipLaunchKernelGGL((k_phi<T, KPv, NCBv, NW, PhiCfg<T>::PRE, S1V>), dim3(grid), dim3(64 * NW), 0,
-                       stream, xg, cvec, V, a_ptr, row0, nrows, ntiles_j, n, d, inv_n, wv, xc, phi);
-    return hipGetLastError();
-}
-#define SVGD_PHI_CASE(KPv, NCBv)                                                             \
-    if (KP == KPv && NCB == NCBv)                                                            \
-        return launch_phi_tile<T, KPv, NCBv, false>(xg, cvec, V, a_ptr, row0, nrows, ntiles_j, \
-                                                    n, d, inv_n, wv, xc, phi, stream);
-#define SVGD_PHI_CASE_S1V(KPv, NCBv)                                                         \
-    if (KP == KPv && NCB == NCBv && d == 16 * NCBv)                                          \
-        return launch_phi_tile<T, KPv, NCBv, true>(xg, cvec, V, a_ptr, row0, nrows, ntiles_j,  \
-                                                   n, d, inv_n, wv, xc, phi, stream);
-
-// S1V tiles (d = 16 NCB > 16: fp64, and F32 under the bf16 matrix-core phi)
-bool phi_tile_s1v(int d) { return d > 16 && d <= 64 && d % 16 == 0; }
-void phi_tile_cfg(bool f64, int *nw, int *pre)
-{
-    *nw = f64 ? PhiCfg<double>::NW : PhiCfg<float>::NW;
-    *pre = f64 ? PhiCfg<double>::PRE : PhiCfg<float>::PRE;
-}
+// the tile classes built for each type (built.h)
+template <class T> static constexpr auto &TILES_OF = TILES_F32;
+template <> constexpr auto &TILES_OF<double> = TILES_F64;
+template <class T> static constexpr auto &PAIR_KP_OF = PAIR_KP_F32;
+template <> constexpr auto &PAIR_KP_OF<double> = PAIR_KP_F64;
 
 template <class T>
-static hipError_t launch_phi_t(int KP, int NCB, const T *xg, const T *cvec, const T *V,
-                               const double *a_ptr, int64_t row0, int64_t nrows, int64_t ntiles_j,
-                               int64_t n, int d, double inv_n, const double *wv, const double *xc,
-                               double *phi, hipStream_t stream)
+hipError_t launch_phi(int KP, int NCB, bool s1v, const T *xg, const T *cvec, const T *V,
+                      const double *a_ptr, int64_t row0, int64_t nrows, int64_t ntiles_j, int64_t n,
+                      int d, double inv_n, const double *wv, const double *xc, double *phi,
+                      hipStream_t stream)
 {
     if (nrows <= 0) return hipSuccess;
-    SVGD_PHI_CASE_S1V(32, 2)
-    SVGD_PHI_CASE_S1V(64, 3)
-    SVGD_PHI_CASE_S1V(64, 4)
-    SVGD_PHI_CASE(4, 1)
-    SVGD_PHI_CASE(8, 1)
-    SVGD_PHI_CASE(12, 1)
-    SVGD_PHI_CASE(16, 1)
-    SVGD_PHI_CASE(16, 2)
-    SVGD_PHI_CASE(32, 2)
-    SVGD_PHI_CASE(32, 3)
-    SVGD_PHI_CASE(64, 4)
-    SVGD_PHI_CASE(64, 5)
-    return hipErrorInvalidValue;
+    constexpr int NW = PhiCfg<T>::NW;
+    const int64_t grid = (nrows + 16 * NW - 1) / (16 * NW);
+    auto launch = [&](auto kp, auto ncb, auto s1) {
+        hipLaunchKernelGGL((k_phi<T, decltype(kp)::value, decltype(ncb)::value, NW, PhiCfg<T>::PRE,
+                                  decltype(s1)::value>),
+                           dim3(grid), dim3(64 * NW), 0, stream, xg, cvec, V, a_ptr, row0, nrows, ntiles_j,
+                           n, d, inv_n, wv, xc, phi);
+    };
+    if (s1v)
+        return launched(dispatch<TILES_S1V>(KP, NCB, [&](auto kp, auto ncb) { launch(kp, ncb, std::true_type{}); }));
+    return launched(dispatch<TILES_OF<T>>(KP, NCB, [&](auto kp, auto ncb) { launch(kp, ncb, std::false_type{}); }));
 }
-#undef SVGD_PHI_CASE
-#undef SVGD_PHI_CASE_S1V
-
-hipError_t launch_phi(int KP, int NCB, const double *xc, const double *cvec, const double *V,
-                      const double *a_ptr, int64_t row0, int64_t nrows, int64_t ntiles_j, int64_t n,
-                      int d, double inv_n, const double *wv, double *phi, hipStream_t stream)
-{
-    return launch_phi_t<double>(KP, NCB, xc, cvec, V, a_ptr, row0, nrows, ntiles_j, n, d, inv_n,
-                                wv, xc, phi, stream);
-}
-
-hipError_t launch_phi_f32(int KP, int NCB, const float *xg, const float *cvec, const float *V,
-                          const double *a_ptr, int64_t row0, int64_t nrows, int64_t ntiles_j,
-                          int64_t n, int d, double inv_n, const double *wv, const double *xc,
-                          double *phi, hipStream_t stream)
-{
-    return launch_phi_t<float>(KP, NCB, xg, cvec, V, a_ptr, row0, nrows, ntiles_j, n, d, inv_n, wv,
-                               xc, phi, stream);
-}
-
-#define SVGD_TILE_CASE(KPv)                                                                  \
-    if (KP == KPv) {                                                                         \
-        if (mode == 0)                                                                       \
-            hipLaunchKernelGGL((k_pair_tiles<T, KPv, 0>), dim3(grid), dim3(256), 0, stream,  \
-                               xc, nrm, n, nb, t0, t1, sc, sh, sd, xk);                          \
-        else if (mode == 1)                                                                  \
-            hipLaunchKernelGGL((k_pair_tiles<T, KPv, 1>), dim3(grid), dim3(256), 0, stream,  \
-                               xc, nrm, n, nb, t0, t1, sc, sh, sd, xk);                          \
-        else if (mode == 2)                                                                  \
-            hipLaunchKernelGGL((k_pair_tiles<T, KPv, 2>), dim3(grid), dim3(256), 0, stream,  \
-                               xc, nrm, n, nb, t0, t1, sc, sh, sd, xk);                          \
-        else                                                                                 \
-            hipLaunchKernelGGL((k_pair_tiles<T, KPv, 3>), dim3(grid), dim3(256), 0, stream,  \
-                               xc, nrm, n, nb, t0, t1, sc, sh, sd, xk);                          \
-        return hipGetLastError();                                                            \
-    }
+template hipError_t launch_phi<double>(int, int, bool, const double *, const double *, const double *,
+                                       const double *, int64_t, int64_t, int64_t, int64_t, int, double,
+                                       const double *, const double *, double *, hipStream_t);
+template hipError_t launch_phi<float>(int, int, bool, const float *, const float *, const float *,
+                                      const double *, int64_t, int64_t, int64_t, int64_t, int, double,
+                                      const double *, const double *, double *, hipStream_t);
 
 template <class T>
-static hipError_t launch_pair_tiles_t(int KP, int mode, int grid, const T *xc, const T *nrm,
-                                      int64_t n, int64_t nb, int64_t t0, int64_t t1,
-                                      uint64_t *regions, int64_t cap, uint32_t *counts,
-                                      unsigned long long *below, const SelState *st,
-                                      unsigned long long *ghist, uint32_t *bpart, double *dbg_out,
-                                      hipStream_t stream, uint64_t *sample_out = nullptr,
-                                      const uint32_t *xk = nullptr)
+hipError_t launch_pair_tiles(int KP, int mode, int grid, const T *xc, const T *nrm, const uint32_t *xk,
+                             const PairArgs &a, hipStream_t stream)
 {
-    if (grid <= 0 || t1 <= t0) return hipSuccess;
+    if (grid <= 0 || a.t1 <= a.t0) return hipSuccess;
     // F32 keys at KP 32 / 64 are the bf16 part-product keys: their parts are required
     if (sizeof(T) == 4 && kb3_keys(KP) && !xk) return hipErrorInvalidValue;
-    SinkCollect sc{st, regions, cap, counts, below, nullptr, nullptr, mode == 0 ? bpart : nullptr};
-    SinkHist sh{st, ghist};
-    SinkDebug sd{dbg_out, n, sample_out};
-    SVGD_TILE_CASE(4)
-    SVGD_TILE_CASE(8)
-    SVGD_TILE_CASE(12)
-    SVGD_TILE_CASE(16)
-    SVGD_TILE_CASE(32)
-    SVGD_TILE_CASE(64)
-    return hipErrorInvalidValue;
+    const PairSinks s(a, mode, nullptr, nullptr);
+    return launched(dispatch<PAIR_KP_OF<T>>(KP, [&](auto kp) {
+        return dispatch<PAIR_TILE_MODES>(mode, [&](auto mc) {
+            hipLaunchKernelGGL((k_pair_tiles<T, decltype(kp)::value, decltype(mc)::value>), dim3(grid),
+                               dim3(256), 0, stream, xc, nrm, a.n, a.nb, a.t0, a.t1, s.sc, s.sh, s.sd, xk);
+        });
+    }));
 }
-#undef SVGD_TILE_CASE
-
-hipError_t launch_pair_tiles(int KP, int mode, int grid, const double *xc, const double *nrm,
-                             int64_t n, int64_t nb, int64_t t0, int64_t t1, uint64_t *regions,
-                             int64_t cap, uint32_t *counts, unsigned long long *below,
-                             const SelState *st, unsigned long long *ghist, uint32_t *bpart,
-                             double *dbg_out, hipStream_t stream)
-{
-    return launch_pair_tiles_t<double>(KP, mode, grid, xc, nrm, n, nb, t0, t1, regions, cap,
-                                       counts, below, st, ghist, bpart, dbg_out, stream);
-}
-
-hipError_t launch_pair_tiles_f32(int KP, int mode, int grid, const float *xc, const float *nrm,
-                                 int64_t n, int64_t nb, int64_t t0, int64_t t1, uint64_t *regions,
-                                 int64_t cap, uint32_t *counts, unsigned long long *below,
-                                 const SelState *st, unsigned long long *ghist, uint32_t *bpart,
-                                 double *dbg_out, const uint32_t *xk, hipStream_t stream)
-{
-    return launch_pair_tiles_t<float>(KP, mode, grid, xc, nrm, n, nb, t0, t1, regions, cap,
-                                      counts, below, st, ghist, bpart, dbg_out, stream, nullptr, xk);
-}
+template hipError_t launch_pair_tiles<double>(int, int, int, const double *, const double *, const uint32_t *,
+                                              const PairArgs &, hipStream_t);
+template hipError_t launch_pair_tiles<float>(int, int, int, const float *, const float *, const uint32_t *,
+                                             const PairArgs &, hipStream_t);
 
 hipError_t launch_sample_tiles(int KP, const double *xc, const double *nrm, const float *xcf,
                                const float *nrmf, const uint32_t *xk, int64_t n, int64_t ntiles,
@@ -4666,12 +4542,12 @@ hipError_t launch_sample_tiles(int KP, const double *xc, const double *nrm, cons
 {
     if (n / TB < 2 || ntiles <= 0) return hipErrorInvalidValue;
     const int grid = (int)(ntiles < 1024 ? ntiles : 1024);
-    if (xcf)
-        return launch_pair_tiles_t<float>(KP, 3, grid, xcf, nrmf, n, 0, 0, ntiles, nullptr, 0,
-                                          nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                          stream, keys, xk);
-    return launch_pair_tiles_t<double>(KP, 3, grid, xc, nrm, n, 0, 0, ntiles, nullptr, 0, nullptr,
-                                       nullptr, nullptr, nullptr, nullptr, nullptr, stream, keys);
+    PairArgs a{};
+    a.n = n;
+    a.t1 = ntiles;
+    a.sample = keys;
+    if (xcf) return launch_pair_tiles<float>(KP, 3, grid, xcf, nrmf, xk, a, stream);
+    return launch_pair_tiles<double>(KP, 3, grid, xc, nrm, nullptr, a, stream);
 }
 
 hipError_t launch_swz_f32(const double *x, int KP, const double *V, int VW, const double *cvec,
@@ -4685,16 +4561,6 @@ hipError_t launch_swz_f32(const double *x, int KP, const double *V, int VW, cons
     return hipGetLastError();
 }
 
-#define SVGD_PHIS_CASE(KPv, NCBv)                                                            \
-    if (KP == KPv && NCB == NCBv) {                                                          \
-        hipLaunchKernelGGL((k_phi_f32s<KPv, NCBv>), dim3(grid), dim3(256), 0, stream, XS, VS, xrow, \
-                           crow, a_ptr, row0, nrows, ntiles, d, inv_n, wv, xc, xc_stride, phi, \
-                           opt ? *opt : OptArgs{}, opt ? 1 : 0);                            \
-        return hipGetLastError();                                                            \
-    }
-
-bool phi_f32s_supported(int KP, int NCB) { return KP % 16 == 0 && KP <= 64 && NCB >= 1 && NCB <= 5; }
-
 hipError_t launch_phi_f32s(int KP, int NCB, const float *XS, const float *VS, const float *xrow,
                            const float *crow, const double *a_ptr, int64_t row0, int64_t nrows,
                            int64_t ntiles, int d, double inv_n, const double *wv, const double *xc,
@@ -4703,15 +4569,13 @@ hipError_t launch_phi_f32s(int KP, int NCB, const float *XS, const float *VS, co
     if (nrows <= 0) return hipSuccess;
     if (row0 % 16) return hipErrorInvalidValue; // (waves own 16-row groups of the padded rows)
     const int64_t grid = (nrows + 63) / 64;
-    SVGD_PHIS_CASE(16, 1) SVGD_PHIS_CASE(16, 2)
-    SVGD_PHIS_CASE(32, 1) SVGD_PHIS_CASE(32, 2) SVGD_PHIS_CASE(32, 3)
-    SVGD_PHIS_CASE(64, 1) SVGD_PHIS_CASE(64, 2) SVGD_PHIS_CASE(64, 3) SVGD_PHIS_CASE(64, 4)
-    SVGD_PHIS_CASE(64, 5)
-    return hipErrorInvalidValue;
+    return launched(dispatch<TILES_F32S>(KP, NCB, [&](auto kp, auto ncb) {
+        hipLaunchKernelGGL((k_phi_f32s<decltype(kp)::value, decltype(ncb)::value>), dim3(grid), dim3(256), 0,
+                           stream, XS, VS, xrow, crow, a_ptr, row0, nrows, ntiles, d, inv_n, wv, xc, xc_stride,
+                           phi, opt ? *opt : OptArgs{}, opt ? 1 : 0);
+    }));
 }
-#undef SVGD_PHIS_CASE
 
-bool phi_b3_supported(int KP, int NCB) { return (KP == 32 || KP == 64) && NCB >= 1 && NCB <= 5; }
 int64_t phi_b3_tile_words(int KP, int NCB) { return (int64_t)(6 * (KP / 32) + 3 * NCB + 2) * 256; }
 
 int64_t median_key_part_words(int KP, int64_t np) { return kb3_keys(KP) ? (np / 16) * kb3_block_words(KP) : 0; }
@@ -4732,7 +4596,8 @@ hipError_t launch_swz_keys_b3(const float *xcf, int KP, int64_t np, uint32_t *XK
 hipError_t launch_swz_b3(const double *x, int KP, const double *V, int VW, const double *cvec,
                          int64_t n, int64_t ntiles, uint32_t *B3, hipStream_t stream)
 {
-    if (!phi_b3_supported(KP, VW / 16) || VW % 16 || ntiles <= 0) return hipErrorInvalidValue;
+    const TileClass t{KP, VW / 16};
+    if (!(built(TILES_B3, t) || built(TILES_S1V, t)) || VW % 16 || ntiles <= 0) return hipErrorInvalidValue;
     const int64_t tot = ntiles * (2 * (KP / 32) + VW / 16) * 64 + ntiles * 128;
     int64_t g = (tot + 255) / 256;
     if (g > 8192) g = 8192;
@@ -4743,42 +4608,30 @@ hipError_t launch_swz_b3(const double *x, int KP, const double *V, int VW, const
     return hipGetLastError();
 }
 
-#ifndef SVGD_B3_NW
-#define SVGD_B3_NW 8
-#endif
-#define SVGD_PHIB3_LAUNCH(KPv, NCBv, S1Vv, RGv)                                               \
-    hipLaunchKernelGGL((k_phi_b3<KPv, NCBv, SVGD_B3_NW, S1Vv, RGv>),                            \
-                       dim3((nrows + 16 * RGv * SVGD_B3_NW - 1) / (16 * RGv * SVGD_B3_NW)),     \
-                       dim3(64 * SVGD_B3_NW), 0, stream, B3, crow, a_ptr, row0, nrows, ntiles, d, \
-                       inv_n, wv, xc, xc_stride, phi, opt ? *opt : OptArgs{}, opt ? 1 : 0)
-#define SVGD_PHIB3_CASE(KPv, NCBv)                                                           \
-    if (KP == KPv && NCB == NCBv) {                                                          \
-        if (d == 16 * NCBv && rg2)                                                            \
-            SVGD_PHIB3_LAUNCH(KPv, NCBv, true, 2);                                            \
-        else if (d == 16 * NCBv)                                                              \
-            SVGD_PHIB3_LAUNCH(KPv, NCBv, true, 1);                                            \
-        else if (rg2)                                                                         \
-            SVGD_PHIB3_LAUNCH(KPv, NCBv, false, 2);                                           \
-        else                                                                                  \
-            SVGD_PHIB3_LAUNCH(KPv, NCBv, false, 1);                                           \
-        return hipGetLastError();                                                            \
-    }
-int phi_b3_rows_per_wg(int rg) { return 16 * rg * SVGD_B3_NW; }
-hipError_t launch_phi_b3(int KP, int NCB, const uint32_t *B3, const float *crow,
+hipError_t launch_phi_b3(int KP, int NCB, bool s1v, const uint32_t *B3, const float *crow,
                          const double *a_ptr, int64_t row0, int64_t nrows, int64_t ntiles, int d,
                          double inv_n, const double *wv, const double *xc, int xc_stride,
                          double *phi, const OptArgs *opt, int rg, hipStream_t stream)
 {
     if (nrows <= 0) return hipSuccess;
     if (row0 % 16) return hipErrorInvalidValue; // (waves own 16-row groups of the padded rows)
-    const bool rg2 = rg == 2;
-    SVGD_PHIB3_CASE(32, 1) SVGD_PHIB3_CASE(32, 2) SVGD_PHIB3_CASE(32, 3)
-    SVGD_PHIB3_CASE(64, 1) SVGD_PHIB3_CASE(64, 2) SVGD_PHIB3_CASE(64, 3) SVGD_PHIB3_CASE(64, 4)
-    SVGD_PHIB3_CASE(64, 5)
-    return hipErrorInvalidValue;
+    constexpr int NW = SVGD_B3_NW;
+    auto launch = [&](auto kp, auto ncb, auto s1) {
+        // (any rg but 2 is one row group per wave)
+        return dispatch<B3_RG>(rg == 2 ? 2 : 1, [&](auto rgc) {
+            constexpr int RG = decltype(rgc)::value;
+            hipLaunchKernelGGL((k_phi_b3<decltype(kp)::value, decltype(ncb)::value, NW, decltype(s1)::value, RG>),
+                               dim3((nrows + 16 * RG * NW - 1) / (16 * RG * NW)), dim3(64 * NW), 0, stream, B3,
+                               crow, a_ptr, row0, nrows, ntiles, d, inv_n, wv, xc, xc_stride, phi,
+                               opt ? *opt : OptArgs{}, opt ? 1 : 0);
+        });
+    };
+    if (s1v)
+        return launched(
+            dispatch<TILES_S1V>(KP, NCB, [&](auto kp, auto ncb) { return launch(kp, ncb, std::true_type{}); }));
+    return launched(
+        dispatch<TILES_B3>(KP, NCB, [&](auto kp, auto ncb) { return launch(kp, ncb, std::false_type{}); }));
 }
-#undef SVGD_PHIB3_CASE
-#undef SVGD_PHIB3_LAUNCH
 
 // fp32 norms for the tile-path median passes: rows [n, np) get +inf, so a
 // padding particle's v = fma(2, dot, -n_i - n_j) is -inf (never below, never
@@ -4835,23 +4688,13 @@ hipError_t launch_mean_center(const double *X, int64_t n, int d, int KP, int64_t
     int64_t g = (np + 255) / 256;
     if (g > 4096) g = 4096;
     const int gd = center_fold_grid(d, np);
-#define SVGD_CENTER_CASE(Dv)                                                                  \
-    case Dv:                                                                                  \
-        hipLaunchKernelGGL((k_center_d<Dv>), dim3(gd), dim3(256), 0, stream, X, n, pin, nin,   \
-                           np, xc, nrm, nrm_in_slot, xf, nmax_bits, nmax_zero, pout, bzero, st_out, \
-                           sinit, reinterpret_cast<uint4 *>(xsplit));                          \
+    // the row stream's records (any other stride: the generic kernels below)
+    if (KP == med_rec_stride(d) && dispatch<ROW_DIMS>(d, [&](auto dc) {
+            hipLaunchKernelGGL((k_center_d<decltype(dc)::value>), dim3(gd), dim3(256), 0, stream, X, n, pin, nin,
+                               np, xc, nrm, nrm_in_slot, xf, nmax_bits, nmax_zero, pout, bzero, st_out, sinit,
+                               reinterpret_cast<uint4 *>(xsplit));
+        }))
         return hipGetLastError();
-    if (d <= 16 && KP == med_rec_stride(d)) {
-        switch (d) {
-            SVGD_CENTER_CASE(1) SVGD_CENTER_CASE(2) SVGD_CENTER_CASE(3) SVGD_CENTER_CASE(4)
-            SVGD_CENTER_CASE(5) SVGD_CENTER_CASE(6) SVGD_CENTER_CASE(7) SVGD_CENTER_CASE(8)
-            SVGD_CENTER_CASE(9) SVGD_CENTER_CASE(10) SVGD_CENTER_CASE(11) SVGD_CENTER_CASE(12)
-            SVGD_CENTER_CASE(13) SVGD_CENTER_CASE(14) SVGD_CENTER_CASE(15) SVGD_CENTER_CASE(16)
-        default:
-            break;
-        }
-    }
-#undef SVGD_CENTER_CASE
     if (xsplit) return hipErrorInvalidValue; // (the split: k_center_d, d <= 8, only)
     if (!xf && !nrm_in_slot && (KP == 32 || KP == 64) && d <= KP && np % 2 == 0) {
         if (KP == 32)
@@ -4888,12 +4731,6 @@ hipError_t launch_opt_update(const OptArgs &o, const double *g, hipStream_t stre
     return hipGetLastError();
 }
 
-#define SVGD_SAMPLE_CASE(Dv)                                                                 \
-    case Dv:                                                                                 \
-        hipLaunchKernelGGL((k_sample_keys_f32<Dv>), dim3(g), dim3(256), 0, stream, xf, n, g0, S, keys, \
-                           init, st_out);                                                    \
-        break;
-
 hipError_t launch_sample_keys(const double *xc, const double *nrm, const float *xf, int64_t n,
                               int d, int KP, int64_t g0, int64_t S, uint64_t *keys,
                               const SelState &init, SelState *st_out, hipStream_t stream)
@@ -4906,15 +4743,10 @@ hipError_t launch_sample_keys(const double *xc, const double *nrm, const float *
                            keys, init, st_out);
         return hipGetLastError();
     }
-    switch (d) {
-        SVGD_SAMPLE_CASE(1) SVGD_SAMPLE_CASE(2) SVGD_SAMPLE_CASE(3) SVGD_SAMPLE_CASE(4)
-        SVGD_SAMPLE_CASE(5) SVGD_SAMPLE_CASE(6) SVGD_SAMPLE_CASE(7) SVGD_SAMPLE_CASE(8)
-        SVGD_SAMPLE_CASE(9) SVGD_SAMPLE_CASE(10) SVGD_SAMPLE_CASE(11) SVGD_SAMPLE_CASE(12)
-        SVGD_SAMPLE_CASE(13) SVGD_SAMPLE_CASE(14) SVGD_SAMPLE_CASE(15) SVGD_SAMPLE_CASE(16)
-    default:
-        return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return launched(dispatch<ROW_DIMS>(d, [&](auto dc) {
+        hipLaunchKernelGGL((k_sample_keys_f32<decltype(dc)::value>), dim3(g), dim3(256), 0, stream, xf, n, g0, S,
+                           keys, init, st_out);
+    }));
 }
 
 hipError_t launch_hist_regions(const uint64_t *keys, const uint32_t *counts, int64_t nreg,
@@ -5057,26 +4889,21 @@ hipError_t launch_prep_v_mat(const double *xc, const double *G, const double *M,
     return hipGetLastError();
 }
 
+// k_gauss_grad<D> with the dimension's loops unrolled, else <0>: any d <= 64
+static constexpr int GAUSS_GRAD_DIMS[] = {1, 2, 3, 4, 5, 6, 7, 8, 12, 16};
 hipError_t launch_gauss_grad(const double *X, int64_t rows, int d, int k, const double *mu,
                              const double *prec, double *G, hipStream_t stream)
 {
     if (rows <= 0) return hipSuccess;
     const int64_t g = (rows + 255) / 256;
-#define SVGD_GG_CASE(Dv)                                                                     \
-    case Dv:                                                                                 \
-        hipLaunchKernelGGL((k_gauss_grad<Dv>), dim3(g), dim3(256), 0, stream, X, rows, d, k, mu, \
-                           prec, G);                                                         \
-        break;
-    switch (d) {
-        SVGD_GG_CASE(1) SVGD_GG_CASE(2) SVGD_GG_CASE(3) SVGD_GG_CASE(4)
-        SVGD_GG_CASE(5) SVGD_GG_CASE(6) SVGD_GG_CASE(7) SVGD_GG_CASE(8)
-        SVGD_GG_CASE(12) SVGD_GG_CASE(16)
-    default:
-        if (d > 64) return hipErrorInvalidValue;
-        hipLaunchKernelGGL((k_gauss_grad<0>), dim3(g), dim3(256), 0, stream, X, rows, d, k, mu,
+    auto launch = [&](auto dc) {
+        hipLaunchKernelGGL((k_gauss_grad<decltype(dc)::value>), dim3(g), dim3(256), 0, stream, X, rows, d, k, mu,
                            prec, G);
+    };
+    if (!dispatch<GAUSS_GRAD_DIMS>(d, launch)) {
+        if (d > 64) return hipErrorInvalidValue;
+        launch(std::integral_constant<int, 0>{});
     }
-#undef SVGD_GG_CASE
     return hipGetLastError();
 }
 
@@ -5088,94 +4915,29 @@ hipError_t launch_finalize(const SelState *st, int navg, int src_lo, int src_hi,
     return hipGetLastError();
 }
 
-} // namespace svgd_amd
+// ---- the symmetric pass: k_prep_sym / k_phi_sym / k_sym_finish / k_sym_apply<D>, D in SYM_DIMS
 
-namespace svgd_amd {
-
-bool phi_sym_supported(int d) { return d >= 1 && d <= 8; }
-
-#define SVGD_SYM_GEOM(Dv)                                                                    \
-    case Dv:                                                                                 \
-        *B = SymGeom<Dv>::B;                                                                 \
-        *SRS = SymGeom<Dv>::SRS;                                                             \
-        *NSUB = SymGeom<Dv>::NSUB;                                                           \
-        return true;
 bool phi_sym_geom(int d, int *B, int *SRS, int *NSUB)
 {
-    switch (d) {
-        SVGD_SYM_GEOM(1) SVGD_SYM_GEOM(2) SVGD_SYM_GEOM(3) SVGD_SYM_GEOM(4)
-        SVGD_SYM_GEOM(5) SVGD_SYM_GEOM(6) SVGD_SYM_GEOM(7) SVGD_SYM_GEOM(8)
-    default:
-        return false;
-    }
+    return dispatch<SYM_DIMS>(d, [&](auto dc) {
+        using Gm = SymGeom<decltype(dc)::value>;
+        *B = Gm::B;
+        *SRS = Gm::SRS;
+        *NSUB = Gm::NSUB;
+    });
 }
+
+static int blocks_per_cu(hipError_t e, int nb) { return (e == hipSuccess && nb > 0) ? nb : 1; }
 
 int phi_sym_blocks_per_cu(int d)
 {
     int nb = 0;
     hipError_t e = hipErrorInvalidValue;
-    switch (d) {
-    case 1: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_phi_sym<1>, SYM_NW * 64, 0); break;
-    case 2: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_phi_sym<2>, SYM_NW * 64, 0); break;
-    case 3: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_phi_sym<3>, SYM_NW * 64, 0); break;
-    case 4: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_phi_sym<4>, SYM_NW * 64, 0); break;
-    case 5: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_phi_sym<5>, SYM_NW * 64, 0); break;
-    case 6: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_phi_sym<6>, SYM_NW * 64, 0); break;
-    case 7: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_phi_sym<7>, SYM_NW * 64, 0); break;
-    case 8: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_phi_sym<8>, SYM_NW * 64, 0); break;
-    default: break;
-    }
-    return (e == hipSuccess && nb > 0) ? nb : 1;
+    dispatch<SYM_DIMS>(d, [&](auto dc) {
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_phi_sym<decltype(dc)::value>, SYM_NW * 64, 0);
+    });
+    return blocks_per_cu(e, nb);
 }
-
-#define SVGD_SYM_CASE(Dv)                                                                     \
-    case Dv: {                                                                                \
-        using Gm = SymGeom<Dv>;                                                               \
-        const int64_t npad = a.nbs * Gm::B;                                                   \
-        int64_t g = (npad + 255) / 256;                                                       \
-        if (g > 4096) g = 4096;                                                               \
-        hipLaunchKernelGGL((k_prep_sym<Dv>), dim3(g), dim3(256), 0, stream, a.xc, a.KP, a.G,   \
-                           a.nrm, a.a_ptr, a.nmax, a.n, npad, a.srec, a.symok, a.rec, a.RS);  \
-        if ((e = hipGetLastError()) != hipSuccess) return e;                                  \
-        if (ev_k0 && (e = hipEventRecord(ev_k0, stream)) != hipSuccess) return e;             \
-        const SymRows fr{a.rec, a.row0, a.nrows, a.n, a.fS,                                   \
-                         ((a.nrows + phi_rows_t8k_rows(4) - 1) / phi_rows_t8k_rows(4)) * a.fS,  \
-                         a.fpart, a.fldp, a.nmax};                                            \
-        hipLaunchKernelGGL((k_phi_sym<Dv>), dim3(a.grid), dim3(SYM_NW * 64), 0, stream, a.srec, a.a_ptr, \
-                           a.nbs, a.u0, a.u1, a.symok, a.rowpart, a.blkg, a.rbase, a.colpart, a.SM, \
-                           a.wst, a.qlast, a.tab8k, fr);                                      \
-        if ((e = hipGetLastError()) != hipSuccess) return e;                                  \
-        if (ev_k1 && (e = hipEventRecord(ev_k1, stream)) != hipSuccess) return e;             \
-        return hipSuccess;                                                                    \
-    }
-
-#define SVGD_SYM_FINISH_CASE(Dv)                                                              \
-    case Dv: {                                                                                \
-        constexpr int RB = 256 / SymGeom<Dv>::DP;                                             \
-        /* P > 1 (contrib): only the particles this rank's units touch -- the    \
-           row blocks Ia .. Ib and up to SM - 1 blocks ahead, a cyclic run;      \
-           the others' sums stay zero from the allocation and are never sent */  \
-        const int64_t B_ = SymGeom<Dv>::B;                                                    \
-        const int64_t fr0 = a.contrib ? a.Ia * B_ : a.row0;                                   \
-        const int64_t fn = a.contrib ? std::min<int64_t>(a.n, (a.Ib - a.Ia + a.SM) * B_) : a.nrows; \
-        if (fn <= 0) return hipSuccess;                                                       \
-        hipLaunchKernelGGL((k_sym_finish<Dv>), dim3((fn + RB - 1) / RB), dim3(256), 0,         \
-                           stream, a.rowpart, a.colpart, a.srec, a.a_ptr, a.nbs, a.SM, a.Ia,   \
-                           a.Ib, a.blkg, a.rbase, a.symok, fr0, fn, a.inv_n, a.phi,            \
-                           opt ? *opt : OptArgs{}, opt ? 1 : 0, a.contrib,                    \
-                           a.contrib ? a.n : (int64_t)0, fb);                                 \
-        return hipGetLastError();                                                             \
-    }
-
-#define SVGD_SYM_APPLY_CASE(Dv)                                                               \
-    case Dv: {                                                                                \
-        constexpr int RB = 256 / SymGeom<Dv>::DP;                                             \
-        hipLaunchKernelGGL((k_sym_apply<Dv>), dim3((a.nrows + RB - 1) / RB), dim3(256), 0,     \
-                           stream, own, recv, xtab, world, rank, a.srec, a.a_ptr, a.symok,     \
-                           a.row0, a.nrows, a.inv_n,                                           \
-                           a.phi, opt ? *opt : OptArgs{}, opt ? 1 : 0, fb);                   \
-        return hipGetLastError();                                                             \
-    }
 
 static SymFallback sym_fallback(const SymArgs &a)
 {
@@ -5188,74 +4950,67 @@ hipError_t launch_sym_apply(const SymArgs &a, const double *own, const double *r
     if (world > 1 && !xtab) return hipErrorInvalidValue;
     if (a.nrows <= 0) return hipSuccess;
     const SymFallback fb = sym_fallback(a);
-    switch (a.d) {
-        SVGD_SYM_APPLY_CASE(1) SVGD_SYM_APPLY_CASE(2) SVGD_SYM_APPLY_CASE(3) SVGD_SYM_APPLY_CASE(4)
-        SVGD_SYM_APPLY_CASE(5) SVGD_SYM_APPLY_CASE(6) SVGD_SYM_APPLY_CASE(7) SVGD_SYM_APPLY_CASE(8)
-    default:
-        return hipErrorInvalidValue;
-    }
+    return launched(dispatch<SYM_DIMS>(a.d, [&](auto dc) {
+        constexpr int D = decltype(dc)::value, RB = 256 / SymGeom<D>::DP;
+        hipLaunchKernelGGL((k_sym_apply<D>), dim3((a.nrows + RB - 1) / RB), dim3(256), 0, stream, own, recv,
+                           xtab, world, rank, a.srec, a.a_ptr, a.symok, a.row0, a.nrows, a.inv_n, a.phi,
+                           opt ? *opt : OptArgs{}, opt ? 1 : 0, fb);
+    }));
 }
 
 hipError_t launch_sym_finish(const SymArgs &a, const OptArgs *opt, hipStream_t stream)
 {
     const SymFallback fb = sym_fallback(a);
-    switch (a.d) {
-        SVGD_SYM_FINISH_CASE(1) SVGD_SYM_FINISH_CASE(2) SVGD_SYM_FINISH_CASE(3) SVGD_SYM_FINISH_CASE(4)
-        SVGD_SYM_FINISH_CASE(5) SVGD_SYM_FINISH_CASE(6) SVGD_SYM_FINISH_CASE(7) SVGD_SYM_FINISH_CASE(8)
-    default:
-        return hipErrorInvalidValue;
-    }
+    return launched(dispatch<SYM_DIMS>(a.d, [&](auto dc) {
+        constexpr int D = decltype(dc)::value, RB = 256 / SymGeom<D>::DP;
+        // P > 1 (contrib): only the particles this rank's units touch -- the
+        // row blocks Ia .. Ib and up to SM - 1 blocks ahead, a cyclic run;
+        // the others' sums stay zero from the allocation and are never sent
+        const int64_t B_ = SymGeom<D>::B;
+        const int64_t fr0 = a.contrib ? a.Ia * B_ : a.row0;
+        const int64_t fn = a.contrib ? std::min<int64_t>(a.n, (a.Ib - a.Ia + a.SM) * B_) : a.nrows;
+        if (fn <= 0) return;
+        hipLaunchKernelGGL((k_sym_finish<D>), dim3((fn + RB - 1) / RB), dim3(256), 0, stream, a.rowpart,
+                           a.colpart, a.srec, a.a_ptr, a.nbs, a.SM, a.Ia, a.Ib, a.blkg, a.rbase, a.symok, fr0, fn,
+                           a.inv_n, a.phi, opt ? *opt : OptArgs{}, opt ? 1 : 0, a.contrib,
+                           a.contrib ? a.n : (int64_t)0, fb);
+    }));
 }
 
 hipError_t launch_phi_sym(const SymArgs &a, hipEvent_t ev_k0, hipEvent_t ev_k1, hipStream_t stream)
 {
-    hipError_t e = hipSuccess;
     if (a.nrows <= 0 && !a.contrib) return hipSuccess; // (P > 1: the rank's units still count)
-    switch (a.d) {
-        SVGD_SYM_CASE(1) SVGD_SYM_CASE(2) SVGD_SYM_CASE(3) SVGD_SYM_CASE(4)
-        SVGD_SYM_CASE(5) SVGD_SYM_CASE(6) SVGD_SYM_CASE(7) SVGD_SYM_CASE(8)
-    default:
-        return hipErrorInvalidValue;
-    }
+    hipError_t e = hipSuccess;
+    const bool found = dispatch<SYM_DIMS>(a.d, [&](auto dc) {
+        constexpr int D = decltype(dc)::value;
+        const int64_t npad = a.nbs * SymGeom<D>::B;
+        int64_t g = (npad + 255) / 256;
+        if (g > 4096) g = 4096;
+        hipLaunchKernelGGL((k_prep_sym<D>), dim3(g), dim3(256), 0, stream, a.xc, a.KP, a.G, a.nrm, a.a_ptr,
+                           a.nmax, a.n, npad, a.srec, a.symok, a.rec, a.RS);
+        if ((e = hipGetLastError()) != hipSuccess) return;
+        if (ev_k0 && (e = hipEventRecord(ev_k0, stream)) != hipSuccess) return;
+        // the row stream's hand-over (symok = 0): its 8-wave work-groups
+        constexpr int rows_wg = RowsKernel<D, ROWS_8W>::G.rows_per_wg(RowsKernel<D, ROWS_8W>::R);
+        const SymRows fr{a.rec,   a.row0, a.nrows, a.n, a.fS, ((a.nrows + rows_wg - 1) / rows_wg) * a.fS,
+                         a.fpart, a.fldp, a.nmax};
+        hipLaunchKernelGGL((k_phi_sym<D>), dim3(a.grid), dim3(SYM_NW * 64), 0, stream, a.srec, a.a_ptr, a.nbs,
+                           a.u0, a.u1, a.symok, a.rowpart, a.blkg, a.rbase, a.colpart, a.SM, a.wst, a.qlast,
+                           a.tab8k, fr);
+        if ((e = hipGetLastError()) != hipSuccess) return;
+        if (ev_k1) e = hipEventRecord(ev_k1, stream);
+    });
+    return found ? e : hipErrorInvalidValue;
 }
 
-#define SVGD_OCC_CASE(Dv)                                                                    \
-    case Dv:                                                                                 \
-        e = R == 1   ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_phi_rows<Dv, 1>, 256, 0) \
-            : R == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_phi_rows<Dv, 2>, 256, 0) \
-                     : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_phi_rows<Dv, 4>, 256, 0); \
-        break;
-
-int phi_rows_blocks_per_cu(int d, int R, int kind)
+int phi_rows_blocks_per_cu(int d, RowsKind kind)
 {
     int nb = 0;
     hipError_t e = hipErrorInvalidValue;
-    if (kind == 2) {
-#define SVGD_T8K_OCC(Dv)                                                                          \
-    case Dv:                                                                                      \
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, SVGD_T8K_KERNEL(Dv), T8K_NW * 64, 0); \
-        break;
-        switch (d) {
-            SVGD_T8K_OCC(1) SVGD_T8K_OCC(2) SVGD_T8K_OCC(3) SVGD_T8K_OCC(4)
-            SVGD_T8K_OCC(5) SVGD_T8K_OCC(6) SVGD_T8K_OCC(7) SVGD_T8K_OCC(8)
-            SVGD_T8K_OCC(9) SVGD_T8K_OCC(10) SVGD_T8K_OCC(11) SVGD_T8K_OCC(12)
-            SVGD_T8K_OCC(13) SVGD_T8K_OCC(14) SVGD_T8K_OCC(15) SVGD_T8K_OCC(16)
-        default:
-            break;
-        }
-#undef SVGD_T8K_OCC
-        return (e == hipSuccess && nb > 0) ? nb : 1;
-    }
-    switch (d) {
-        SVGD_OCC_CASE(1) SVGD_OCC_CASE(2) SVGD_OCC_CASE(3) SVGD_OCC_CASE(4)
-        SVGD_OCC_CASE(5) SVGD_OCC_CASE(6) SVGD_OCC_CASE(7) SVGD_OCC_CASE(8)
-        SVGD_OCC_CASE(9) SVGD_OCC_CASE(10) SVGD_OCC_CASE(11) SVGD_OCC_CASE(12)
-        SVGD_OCC_CASE(13) SVGD_OCC_CASE(14) SVGD_OCC_CASE(15) SVGD_OCC_CASE(16)
-    default:
-        break;
-    }
-    return (e == hipSuccess && nb > 0) ? nb : 1;
+    with_rows_kernel(d, kind, [&](auto kernel, int threads) {
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, threads, 0);
+    });
+    return blocks_per_cu(e, nb);
 }
 
 } // namespace svgd_amd
-

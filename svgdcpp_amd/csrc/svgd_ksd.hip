@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dispatch.h"
 #include "svgd_ksd.h"
 
 namespace svgd_amd {
@@ -417,17 +418,9 @@ __global__ __launch_bounds__(KSD_FIN_THREADS) void k_ksd_final(const double *__r
 int ksd_blocks_per_cu(int d)
 {
     const void *f = reinterpret_cast<const void *>(&ksd::k_ksd_tile);
-#define SVGD_KSD_CASE(Dv)                                                  \
-    case Dv:                                                               \
-        f = reinterpret_cast<const void *>(&ksd::k_ksd_rows<Dv>);          \
-        break;
-    switch (d) {
-        SVGD_KSD_CASE(1) SVGD_KSD_CASE(2) SVGD_KSD_CASE(3) SVGD_KSD_CASE(4)
-        SVGD_KSD_CASE(5) SVGD_KSD_CASE(6) SVGD_KSD_CASE(7) SVGD_KSD_CASE(8)
-        SVGD_KSD_CASE(9) SVGD_KSD_CASE(10) SVGD_KSD_CASE(11) SVGD_KSD_CASE(12)
-        SVGD_KSD_CASE(13) SVGD_KSD_CASE(14) SVGD_KSD_CASE(15) SVGD_KSD_CASE(16)
-    }
-#undef SVGD_KSD_CASE
+    dispatch_range<1, 16>(d, [&](auto dc) {
+        f = reinterpret_cast<const void *>(&ksd::k_ksd_rows<decltype(dc)::value>);
+    });
     hipFuncAttributes fa;
     if (hipFuncGetAttributes(&fa, f) != hipSuccess) return 2;
     // 4 waves per work-group on 4 SIMDs: work-groups per CU = waves per SIMD
@@ -479,18 +472,10 @@ hipError_t launch_ksd_pairs(int d, double a, const double *rec, const double *xt
                            diag, a, d, ksd_kp(d), row0, nrows, n, np, S, part, ldp);
         return hipGetLastError();
     }
-#define SVGD_KSD_CASE(Dv)                                                                          \
-    case Dv:                                                                                       \
-        hipLaunchKernelGGL(ksd::k_ksd_rows<Dv>, dim3((unsigned)grid), dim3(256), 0, stream, rec,   \
-                           cvec, diag, a, row0, nrows, n, S, part, ldp);                           \
-        break;
-    switch (d) {
-        SVGD_KSD_CASE(1) SVGD_KSD_CASE(2) SVGD_KSD_CASE(3) SVGD_KSD_CASE(4)
-        SVGD_KSD_CASE(5) SVGD_KSD_CASE(6) SVGD_KSD_CASE(7) SVGD_KSD_CASE(8)
-        SVGD_KSD_CASE(9) SVGD_KSD_CASE(10) SVGD_KSD_CASE(11) SVGD_KSD_CASE(12)
-        SVGD_KSD_CASE(13) SVGD_KSD_CASE(14) SVGD_KSD_CASE(15) SVGD_KSD_CASE(16)
-    }
-#undef SVGD_KSD_CASE
+    dispatch_range<1, 16>(d, [&](auto dc) {
+        hipLaunchKernelGGL(ksd::k_ksd_rows<decltype(dc)::value>, dim3((unsigned)grid), dim3(256), 0, stream, rec,
+                           cvec, diag, a, row0, nrows, n, S, part, ldp);
+    });
     return hipGetLastError();
 }
 

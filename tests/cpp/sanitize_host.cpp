@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <iterator>
 #include <vector>
 
 #include "../../include/svgdcpp_amd/svgd_capi.h"
@@ -107,13 +108,104 @@ static void test_plan()
     CHECK(svgd_plan_bucket_select(cnt.data(), 2048, 2, bad, bsel, rin, &tot) == -1);
 }
 
+// The entries of one list of built.h that the enumerated plans name.
+template <auto &LIST> struct Named {
+    bool hit[std::size(LIST)] = {};
+    template <class T> void name(const T &v) // (a) a plan names built instantiations only
+    {
+        for (size_t i = 0; i < std::size(LIST); ++i)
+            if (LIST[i] == v) {
+                hit[i] = true;
+                return;
+            }
+        CHECK(!"the plan names an instantiation that is not in the built list");
+    }
+    void all_named(const char *list) const // (b) nothing is built that no plan names
+    {
+        for (size_t i = 0; i < std::size(LIST); ++i)
+            if (!hit[i]) {
+                std::fprintf(stderr, "built, but named by no plan: %s entry %zu\n", list, i);
+                ++failures;
+            }
+    }
+};
+
+// Every kernel instantiation a plan stands for -- the phi kernel, and the
+// median pair passes a context of that plan launches -- against the lists the
+// launchers dispatch over.
+struct NamedKernels {
+    Named<svgd_amd::ROW_DIMS> rows[2], pair_rows; // k_phi_rows by RowsKind; k_pair_rows
+    Named<svgd_amd::SYM_DIMS> sym;
+    Named<svgd_amd::TILES_F64> f64;
+    Named<svgd_amd::TILES_F32> f32;
+    Named<svgd_amd::TILES_S1V> s1v_f64, s1v_f32, b3_s1v[std::size(svgd_amd::B3_RG)];
+    Named<svgd_amd::TILES_F32S> f32s;
+    Named<svgd_amd::TILES_B3> b3[std::size(svgd_amd::B3_RG)];
+    Named<svgd_amd::PAIR_KP_F64> pair_f64; // k_pair_tiles<double>
+    Named<svgd_amd::PAIR_KP_F32> pair_f32; // k_pair_tiles<float>, k_pair_tcol / k_pair_tcol3
+
+    void name(const svgd_amd::PhiPlan &p, int dtype)
+    {
+        using namespace svgd_amd;
+        const TileClass t{p.KP, p.NCB};
+        switch (p.path) {
+        case PHI_SYM:
+            sym.name(p.dim);
+            break;
+        case PHI_ROWS:
+            CHECK(p.R == phi_rows_per_lane(p.dim)); // the only R built
+            rows[p.rows_kind].name(p.dim);
+            break;
+        case PHI_TILE_F64:
+            p.s1v ? s1v_f64.name(t) : f64.name(t);
+            break;
+        case PHI_TILE_F32:
+            p.s1v ? s1v_f32.name(t) : f32.name(t);
+            break;
+        case PHI_F32S:
+            CHECK(!p.s1v);
+            f32s.name(t);
+            break;
+        case PHI_B3:
+            CHECK(built(B3_RG, p.b3_rg));
+            for (size_t i = 0; i < std::size(B3_RG); ++i)
+                if (B3_RG[i] == p.b3_rg) p.s1v ? b3_s1v[i].name(t) : b3[i].name(t);
+            break;
+        }
+        if (p.rows())
+            pair_rows.name(p.dim);
+        else if (dtype == SVGD_F32)
+            pair_f32.name(p.KP);
+        else
+            pair_f64.name(p.KP);
+    }
+    void all_named() const
+    {
+        rows[svgd_amd::ROWS_4W].all_named("ROW_DIMS (k_phi_rows, 4 waves)");
+        rows[svgd_amd::ROWS_8W].all_named("ROW_DIMS (k_phi_rows, 8 waves)");
+        pair_rows.all_named("ROW_DIMS (k_pair_rows)");
+        sym.all_named("SYM_DIMS");
+        f64.all_named("TILES_F64");
+        f32.all_named("TILES_F32");
+        s1v_f64.all_named("TILES_S1V (k_phi<double>)");
+        s1v_f32.all_named("TILES_S1V (k_phi<float>)");
+        f32s.all_named("TILES_F32S");
+        for (auto &b : b3) b.all_named("TILES_B3, for one of B3_RG");
+        for (auto &b : b3_s1v) b.all_named("TILES_S1V (k_phi_b3), for one of B3_RG");
+        pair_f64.all_named("PAIR_KP_F64");
+        pair_f32.all_named("PAIR_KP_F32");
+    }
+};
+
 // plan_phi over every dimension, both dtypes, three world sizes and the A/B
-// knobs, with the capability flags as the launchers answer them today
-// (svgd_kernels.hip: phi_*_supported, phi_tile_s1v, med_rec_stride).
+// knobs, with the capability flags the library uses (built.h: phi_caps over
+// the lists the launchers instantiate).  Both ways: every plan, its
+// matrix-scale variant and the median passes they imply name a built
+// instantiation, and every built instantiation is named by some plan.
 static void test_phi_plan()
 {
     using namespace svgd_amd;
-    std::vector<Knobs> settings(8);
+    std::vector<Knobs> settings(9);
     settings[1].phi_tile_generic = true;
     settings[2].phi_b3 = {true, 0};
     settings[3].phi_s1v = {true, 0};
@@ -121,29 +213,36 @@ static void test_phi_plan()
     settings[5].phi_sym = {true, 0};
     settings[6].phi_sym = {true, 1};
     settings[7].phi_sym = {true, 2};
+    // (two knobs at once: the ones-column k_phi_b3 of d = 32 / 64 with two row groups)
+    settings[8].phi_s1v = {true, 0};
+    settings[8].phi_b3_rg = {true, 2};
     PhiPlan p;
     char name[96];
-    PhiCaps c8{};
-    c8.rows_kp = 12, c8.rows_t8k = c8.sym = true;
+    const PhiCaps c8 = phi_caps(8, false);
+    CHECK(c8.rows_kp == 12 && c8.sym);
     CHECK(plan_phi(8, 65536, SVGD_F64, 1, 0, settings[0], c8, &p));
     phi_plan_name(p, c8, name, (int)sizeof name);
     CHECK(std::strcmp(name, "k_phi_sym<8>") == 0);
+    phi_plan_name(matrix_scale_plan(p), c8, name, (int)sizeof name);
+    CHECK(std::strcmp(name, "k_phi_rows<8, 4, 4, 4096, 1>") == 0);
     CHECK(plan_phi(8, 333, SVGD_F64, 1, 0, settings[0], c8, &p));
     phi_plan_name(p, c8, name, (int)sizeof name);
     CHECK(std::strcmp(name, "k_phi_rows<8, 4, 8, 8192, 8>") == 0);
-    CHECK(!plan_phi(65, 333, SVGD_F64, 1, 0, settings[0], PhiCaps{}, &p));
-    CHECK(!plan_phi(0, 333, SVGD_F64, 1, 0, settings[0], PhiCaps{}, &p));
+    CHECK(!plan_phi(65, 333, SVGD_F64, 1, 0, settings[0], phi_caps(65, false), &p));
+    CHECK(!plan_phi(0, 333, SVGD_F64, 1, 0, settings[0], phi_caps(0, false), &p));
+    NamedKernels named;
     for (int d = 1; d <= 64; ++d) {
         int KP = 0, NCB = 0;
         CHECK(pick_tiles(d, &KP, &NCB));
-        PhiCaps cap{};
-        cap.rows_kp = d <= 16 ? ((d + 1 + 3) / 4) * 4 : 0;
-        cap.rows_t8k = d <= 16;
-        cap.sym = d <= 8;
-        cap.tile_s1v = d > 16 && d % 16 == 0;
-        cap.f32s = KP % 16 == 0;
-        cap.b3 = KP == 32 || KP == 64;
-        cap.b3_waves = 8;
+        {
+            // what the lists must amount to, stated by dimension
+            const PhiCaps cap = phi_caps(d, false);
+            CHECK(cap.rows_kp == (d <= 16 ? ((d + 1 + 3) / 4) * 4 : 0));
+            CHECK(cap.sym == (d <= 8));
+            CHECK(cap.tile_s1v == (d > 16 && d % 16 == 0));
+            CHECK(cap.f32s == (KP % 16 == 0));
+            CHECK(cap.b3 == (KP == 32 || KP == 64));
+        }
         for (int dtype : {SVGD_F64, SVGD_F32})
             for (int world : {1, 2, 8})
                 for (int64_t n : {int64_t(333), int64_t(65536)})
@@ -151,10 +250,12 @@ static void test_phi_plan()
                         for (const Knobs &k : settings) {
                             int64_t r0, r1;
                             svgd_plan_rows(n, world, rank, &r0, &r1);
-                            CHECK(plan_phi(d, n, dtype, world, r0, k, cap, &p));
                             const bool f32 = dtype == SVGD_F32;
-                            cap.tile_waves = f32 ? 4 : 8; // PhiCfg<T> in svgd_kernels.hip
-                            cap.tile_pre = !f32;
+                            const PhiCaps cap = phi_caps(d, f32);
+                            CHECK(cap.tile_waves == (f32 ? 4 : 8) && cap.tile_pre == !f32 && cap.b3_waves == 8);
+                            CHECK(plan_phi(d, n, dtype, world, r0, k, cap, &p));
+                            named.name(p, dtype);
+                            named.name(matrix_scale_plan(p), dtype);
                             char name[8]; // (shorter than any name: the formatter must truncate)
                             phi_plan_name(p, cap, name, (int)sizeof name);
                             CHECK(std::strlen(name) == sizeof name - 1 && std::strncmp(name, "k_phi", 5) == 0);
@@ -165,7 +266,7 @@ static void test_phi_plan()
                             CHECK(p.VW >= d + (p.s1v ? 0 : 1));
                             if (p.s1v) CHECK(cap.tile_s1v && !k.phi_s1v.set && (!f32 || cap.b3));
                             if (!f32 && d <= 16) {
-                                CHECK(p.rows() && p.KP == cap.rows_kp && p.R == (d <= 8 ? 4 : 2) && p.rows_kind == 2);
+                                CHECK(p.rows() && p.KP == cap.rows_kp && p.R == (d <= 8 ? 4 : 2) && p.rows_kind == ROWS_8W);
                                 if (p.path == PHI_SYM) CHECK(d <= 8 && k.phi_sym.or_(1) != 0);
                                 if (k.phi_sym.set) CHECK((p.path == PHI_SYM) == (d <= 8 && k.phi_sym.v != 0));
                                 else CHECK((p.path == PHI_SYM) == (d <= 8 && n >= 32768 && n / world >= 8192));
@@ -182,6 +283,7 @@ static void test_phi_plan()
                             CHECK(p.fused() == (p.path != PHI_TILE_F64 && p.path != PHI_TILE_F32));
                         }
     }
+    named.all_named();
 }
 
 static void test_models_vs_oracle()

@@ -1,7 +1,8 @@
 """Every per-dimension kernel instantiation against the oracle.
 
-The launchers in svgd_kernels.hip / svgd_collect.hip switch over d (or over
-the (KP, NCB) tile class pick_tiles derives from d); each case is its own
+The launchers in svgd_kernels.hip / svgd_collect.hip dispatch over d (or over
+the (KP, NCB) tile class pick_tiles derives from d), through the lists of
+built.h; each entry is its own
 compiled kernel with its own register budget, record stride, LDS layout and
 unroll.  This module walks d over every value a user can pick (1..64) with the
 smallest shapes that still reach the code in question, so a wrong bound or
@@ -9,7 +10,8 @@ stride in one instantiation cannot ship with a green suite:
 
   1. the dispatch table: which phi kernel each (dtype, d) launches;
   2. fp64 row-stream phi (k_phi_rows<D, R, 8, 8192, 8> + k_phi_reduce), d 1..16;
-  3. fp64 full-matrix scale (k_prep_rec_mat + k_phi_rows<D, R> kind 0), d 1..16;
+  3. fp64 full-matrix scale (k_prep_rec_mat + k_phi_rows<D, R, 4, 4096, 1>, the
+     4-wave geometry), d 1..16;
   4. fp64 steps (median + phi + the fused optimizer epilogue + host gradient);
   5. fp64 median, direct (k_center_d, k_pair_rows) and bracket
      (k_sample_keys_f32, k_pair_mcol, k_pair_rows) paths, d 1..16, and the
@@ -138,7 +140,7 @@ def _indefinite(d, seed):
 @pytest.mark.parametrize("kind", ["spd", "indefinite"])
 @pytest.mark.parametrize("d", range(1, 17))
 def test_matrix_scale_phi_every_d(oracle, d, kind):
-    """k_prep_rec_mat + k_phi_rows<D, R> (kind 0, signature rows) at n = 777:
+    """k_prep_rec_mat + k_phi_rows<D, R, 4, 4096, 1> (signature rows) at n = 777:
     an SPD M (X scale 2, M / d) and an indefinite one (X scale 1, M / 2 d),
     built as tests/test_gpu_matrix_scale.py builds them."""
     n = 777

@@ -7,9 +7,9 @@ ARCH ?= gfx950
 HIPFLAGS ?= -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wall -Wno-unused-result
 SRC_DIR := svgdcpp_amd/csrc
 LIB := svgdcpp_amd/libsvgdcpp_amd.so
-OBJS := $(SRC_DIR)/svgd_kernels.o $(SRC_DIR)/svgd_collect.o $(SRC_DIR)/svgd_ksd.o $(SRC_DIR)/svgd_capi.o $(SRC_DIR)/plan.o $(SRC_DIR)/host_models.o \
+OBJS := $(SRC_DIR)/svgd_kernels.o $(SRC_DIR)/svgd_collect.o $(SRC_DIR)/svgd_ksd.o $(SRC_DIR)/svgd_capi.o $(SRC_DIR)/plan.o $(SRC_DIR)/median_plan.o $(SRC_DIR)/host_models.o \
         $(SRC_DIR)/hostcomm.o $(SRC_DIR)/svgd_glm.o $(SRC_DIR)/host_glm.o
-HDRS := $(SRC_DIR)/svgd_kernels.h $(SRC_DIR)/built.h $(SRC_DIR)/dispatch.h $(SRC_DIR)/plan.h $(SRC_DIR)/svgd_ksd.h $(SRC_DIR)/svgd_device.h $(SRC_DIR)/svgd_exp_table.h \
+HDRS := $(SRC_DIR)/svgd_kernels.h $(SRC_DIR)/select_state.h $(SRC_DIR)/median_plan.h $(SRC_DIR)/built.h $(SRC_DIR)/dispatch.h $(SRC_DIR)/plan.h $(SRC_DIR)/svgd_ksd.h $(SRC_DIR)/svgd_device.h $(SRC_DIR)/svgd_exp_table.h \
         $(SRC_DIR)/svgd_glm.h $(SRC_DIR)/host_glm.h include/svgdcpp_amd/svgd_capi.h
 
 all: $(LIB)
@@ -27,6 +27,9 @@ $(SRC_DIR)/svgd_capi.o: $(SRC_DIR)/svgd_capi.cpp $(HDRS)
 
 # host-only translation units (no device code)
 $(SRC_DIR)/plan.o: $(SRC_DIR)/plan.cpp $(HDRS)
+	$(CXX) -O3 -std=c++17 -fPIC -Wall -c $< -o $@
+
+$(SRC_DIR)/median_plan.o: $(SRC_DIR)/median_plan.cpp $(HDRS)
 	$(CXX) -O3 -std=c++17 -fPIC -Wall -c $< -o $@
 
 $(SRC_DIR)/hostcomm.o: $(SRC_DIR)/hostcomm.cpp $(SRC_DIR)/hostcomm.h
@@ -77,14 +80,15 @@ build/test_glm: tests/cpp/test_glm.cpp $(CPP_HDRS) $(LIB)
 	@mkdir -p build
 	$(CXX) $(CPP_FLAGS) $< -o $@ $(CPP_LINK)
 
-# Host-code sanitizers (ASan + UBSan): planner, host models and the CPU oracle
+# Host-code sanitizers (ASan + UBSan): planners (phi and median), host models and the CPU oracle
 # linked into a self-checking driver (the HIP host code needs a GPU: see
 # tests/cpp/sanitize_host.cpp).  Run by tests/test_sanitize.py.
 SAN := -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=all
-build/sanitize_host: tests/cpp/sanitize_host.cpp $(SRC_DIR)/plan.cpp $(SRC_DIR)/plan.h $(SRC_DIR)/built.h $(SRC_DIR)/host_models.cpp oracle/svgd_oracle.c
+build/sanitize_host: tests/cpp/sanitize_host.cpp $(SRC_DIR)/plan.cpp $(SRC_DIR)/plan.h $(SRC_DIR)/built.h $(SRC_DIR)/median_plan.cpp $(SRC_DIR)/median_plan.h $(SRC_DIR)/select_state.h $(SRC_DIR)/host_models.cpp oracle/svgd_oracle.c
 	@mkdir -p build/san
 	gcc -O1 -g -std=c11 -fopenmp -ffp-contract=off $(SAN) -c oracle/svgd_oracle.c -o build/san/oracle.o
 	$(CXX) -O1 -g -std=c++17 -fopenmp $(SAN) -c $(SRC_DIR)/plan.cpp -o build/san/plan.o
+	$(CXX) -O1 -g -std=c++17 -fopenmp $(SAN) -c $(SRC_DIR)/median_plan.cpp -o build/san/median_plan.o
 	$(CXX) -O1 -g -std=c++17 -fopenmp $(SAN) -c $(SRC_DIR)/host_models.cpp -o build/san/host_models.o
 	$(CXX) -O1 -g -std=c++17 -fopenmp $(SAN) tests/cpp/sanitize_host.cpp build/san/*.o -o $@ -lm
 

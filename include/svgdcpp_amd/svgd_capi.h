@@ -421,6 +421,44 @@ void svgd_plan_sym_exchange(int64_t n, int block, int nsub, int world, int src, 
  * Returns 0, or -1 if a rank lies past the counted candidates. */
 int svgd_plan_bucket_select(const unsigned long long *counts, int nb, int nsel,
                             const int64_t *ranks, int *bsel, int64_t *rank_in, int64_t *total);
+/* The median's host policy as the library runs it, without a context or a GPU.
+ *
+ * Tracked bracket: the next median of D^2 predicted from the last selected
+ * ones.  A tracker (new: the half-width's multiple of the recent prediction
+ * errors and its relative floor; NULL if out of memory) per trajectory;
+ * restart forgets the history (new particles).  Per step: begin_step, then
+ * predict -- 1 and the bracket [*lo_key, *hi_key) as key bit patterns, its
+ * expected share *band of `pairs` pairs, the predicted D^2 *pred and the
+ * relative half-width *width, or 0: sample the bracket (band_samp: the
+ * sampled bracket's share, which the predicted one must not exceed) -- then
+ * record with the step's selected keys (lower and upper order statistic; error
+ * != 0: the selection failed or went another way, the history restarts), the
+ * bracket they were selected from and its candidate count over all ranks. */
+void *svgd_plan_tracker_new(double err_mult, double min_width);
+void svgd_plan_tracker_free(void *tracker);
+void svgd_plan_tracker_restart(void *tracker);
+void svgd_plan_tracker_begin_step(void *tracker);
+int svgd_plan_tracker_predict(void *tracker, double pairs, double band_samp, uint64_t *lo_key,
+                              uint64_t *hi_key, double *band, double *pred, double *width);
+void svgd_plan_tracker_record(void *tracker, uint64_t key_lo, uint64_t key_hi, int error,
+                              uint64_t bracket_lo_key, uint64_t bracket_hi_key, uint64_t cand);
+/* The bracket sample of a step over n particles: its size (the return value)
+ * and *band_samp, its bracket's expected share of the pairs.  tile_kernels:
+ * the median runs on the tile kernels (d > 16 or F32: whole 64 x 64 tiles are
+ * drawn), else scattered pairs; forced: a set sample size (0: automatic);
+ * multi: more than one rank shares the step; shard_sample: ranks draw
+ * disjoint parts (SVGD_SAMPLE_SHARD); sim_world: svgd_create_sim's (else 1);
+ * bracket_sigma: sample-quantile standard deviations either side. */
+int64_t svgd_plan_median_sample(int64_t n, int tile_kernels, int64_t forced, int multi, int shard_sample,
+                                int sim_world, double bracket_sigma, double *band_samp);
+/* The sample ranks [*slo, *shi] bracketing the quantiles qlo <= qhi of a
+ * sample of S keys, sigma standard deviations either side, and *band_est
+ * (optional), the bracket's expected share of the pairs. */
+void svgd_plan_sample_ranks(int64_t S, double qlo, double qhi, double sigma, int64_t *slo, int64_t *shi,
+                            double *band_est);
+/* Per-rank key capacity of a speculative step's segment after a selection
+ * whose selected buckets held last_tot keys over all ranks. */
+int64_t svgd_plan_spec_cap(int64_t last_tot);
 
 #ifdef __cplusplus
 }

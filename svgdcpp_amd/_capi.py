@@ -45,6 +45,7 @@ SVGD_DIAG_LEN = len(DIAG_NAMES)
 
 _D = ctypes.POINTER(ctypes.c_double)
 _I64 = ctypes.c_int64
+_U64 = ctypes.c_uint64
 _P = ctypes.c_void_p
 
 # name -> (restype, argtypes); every function declared in svgd_capi.h
@@ -106,6 +107,18 @@ SIGNATURES = {
     "svgd_plan_bucket_select": (ctypes.c_int, [ctypes.POINTER(ctypes.c_ulonglong), ctypes.c_int, ctypes.c_int,
                                                ctypes.POINTER(_I64), ctypes.POINTER(ctypes.c_int),
                                                ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
+    "svgd_plan_tracker_new": (_P, [ctypes.c_double, ctypes.c_double]),
+    "svgd_plan_tracker_free": (None, [_P]),
+    "svgd_plan_tracker_restart": (None, [_P]),
+    "svgd_plan_tracker_begin_step": (None, [_P]),
+    "svgd_plan_tracker_predict": (ctypes.c_int, [_P, ctypes.c_double, ctypes.c_double, ctypes.POINTER(_U64),
+                                                 ctypes.POINTER(_U64), _D, _D, _D]),
+    "svgd_plan_tracker_record": (None, [_P, _U64, _U64, ctypes.c_int, _U64, _U64, _U64]),
+    "svgd_plan_median_sample": (_I64, [_I64, ctypes.c_int, _I64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                       ctypes.c_double, _D]),
+    "svgd_plan_sample_ranks": (None, [_I64, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                      ctypes.POINTER(_I64), ctypes.POINTER(_I64), _D]),
+    "svgd_plan_spec_cap": (_I64, [_I64]),
     "svgd_model_create": (ctypes.c_int, [ctypes.POINTER(_P), ctypes.c_int, ctypes.c_int, _D, _D]),
     "svgd_model_destroy": (ctypes.c_int, [_P]),
     "svgd_model_logp_grad": (ctypes.c_int, [_P, _D, _I64, _D]),

@@ -29,6 +29,7 @@
 #include "../../include/svgdcpp_amd/svgd_capi.h"
 #include "svgd_kernels.h"
 #include "plan.h"
+#include "median_plan.h"
 #include "svgd_ksd.h"
 #include "svgd_glm.h"
 #include "hostcomm.h"
@@ -251,11 +252,8 @@ struct svgd_ctx {
     int64_t collect_blocks = 1024; // collect-pass work-groups (4 per CU resident; 5 for the bf16-split mcol)
     bool mcol = true;              // bracket collect on the matrix cores (k_pair_mcol / _tcol)
     uint32_t *xsplit = nullptr;    // its operands, [hi | lo] bf16 x 8 per particle (the centring writes them)
-    double band_est = 1.0;         // this step's bracket: expected share of the pairs
-    bool samp_shard = false;    // this step's sample is sharded
-    int64_t samp_local = 0;     // sample keys held by this rank
-    int64_t samp_S = 0;         // this step's sample: size and target quantiles
-    double samp_qlo = 0.0, samp_qhi = 0.0;
+    double band_est = 1.0;         // this step's bracket (sampled or predicted): expected share of the pairs
+    SamplePlan samp;               // this step's bracket sample (trk_plan; its draw: median_begin)
     int64_t cand_capacity = 0; // 0 = automatic
     uint64_t *sample_keys = nullptr;
     int64_t sample_alloc = 0;
@@ -267,7 +265,7 @@ struct svgd_ctx {
     uint64_t *gseg = nullptr;          // world x (CAPG + 1): compacted selected-bucket keys
     int64_t bucket_cap = CAPG;         // bucket select path if the selected buckets hold <= this
     int64_t last_tot = 0;              // the last selection's selected-bucket keys (all ranks)
-    int64_t spec_cap = CAPR_MIN;       // this speculative step's segment capacity (plan_step)
+    int64_t spec_cap = CAPR_MIN;       // this speculative step's segment capacity (spec_segment_cap)
     uint32_t *counts = nullptr;
     unsigned long long *below = nullptr;
     int collect_grid = 0;
@@ -282,9 +280,7 @@ struct svgd_ctx {
     // per-step median plan (set in begin, consumed in finish)
     int med_path = SVGD_MEDIAN_DIRECT;
     int64_t reg_cap = 0;
-    int nsel = 0;
-    int64_t sel_rank[2] = {0, 0};
-    int src_lo = -1, src_hi = -1, navg = 1;
+    RankPlan sel; // the ranks to select and the statistics averaged (plan_ranks)
     bool median_pending = false;
 
     // pinned host
@@ -390,7 +386,7 @@ struct svgd_ctx {
     // start.
     hipEvent_t ev_status_use = nullptr, ev_fin_use = nullptr, mark = nullptr;
     // timing off: the speculative step's status is known from this sequence
-    // number, stored by the selection into h_trk[8] (no event); 0: by event
+    // number, stored by the selection into h_trk[TRK_SEQ] (no event); 0: by event
     uint64_t status_seq = 0, seq_ctr = 0;
     // likewise at the step's end: the phi phase's end event (timing) doubles
     // as X_t-final for the copy stream (ev_xready_use) when nothing follows it
@@ -398,25 +394,10 @@ struct svgd_ctx {
     hipEvent_t last_phi_end = nullptr; // the last phi phase's end (timing): the next median's start
     double *bak = nullptr; // [X_t | m_t | v_t] of this rank's rows for the pending step
 
-    // Bracket tracking (speculative steps): the median of D^2 moves
-    // smoothly from step to step, so the collect pass's bracket is predicted
-    // from the last selected keys (quadratic extrapolation, half-width 4x the
-    // largest of the last 3 prediction errors) instead of a sample and its two
-    // radix passes.  The selection stays exact; a bracket that misses the order
-    // statistics is a failed plan, and the step is redone with a sample.
-    bool trk_allowed = true;    // SVGD_TRACK_BRACKET=0 disables
-    double trk_err_mult = 4.0;  // SVGD_TRACK_ERR_MULT: half-width / recent error (set at creation)
-    uint64_t *h_trk = nullptr, *h_trk_dev = nullptr; // pinned [lo, hi, below, cand, key0, key1, err]
-    double trk_m[4] = {0, 0, 0, 0}; // last selected D^2 (lower order statistic), newest first
-    int trk_n = 0;
-    double trk_err[3] = {0, 0, 0}; // recent relative errors of the quadratic extrapolation
-    int trk_nerr = 0;
-    double trk_errc[3] = {0, 0, 0}; // ... and of the cubic one (4 medians)
-    int trk_nerrc = 0;
-    double trk_pq = -1, trk_pc = -1; // this step's two extrapolations (< 0: none)
-    double trk_dens = 0;        // candidates per unit of D^2 in the last bracket (all ranks)
-    double trk_gap = 0;         // (upper - lower selected D^2) / lower of the last selection
-    double trk_pred = -1;       // this step's predicted median D^2 (< 0: sampled bracket)
+    // Bracket tracking (median_plan.h): the history, this step's prediction
+    // and the counters; what follows is the step's bookkeeping around it
+    BracketTracker trk;
+    uint64_t *h_trk = nullptr, *h_trk_dev = nullptr; // pinned, TRK_LEN slots (select_state.h TrkSlot)
     bool trk_go = false;        // this step's bracket is the predicted one (trk_plan)
     uint64_t trk_lo = 0, trk_hi = 0;
     double trk_band = 0;        // its expected share of the pairs
@@ -424,8 +405,6 @@ struct svgd_ctx {
     // a synchronous step's selection to add to the history (resolve_pending):
     // 1 its keys are in h_trk / h_cnt, 2 it took another path (history restarts)
     int trk_sync = 0;
-    int64_t trk_steps = 0, trk_miss = 0;
-    double trk_band_sum = 0;    // their predicted band shares (svgd_get_diagnostics)
     // path counters (svgd_get_diagnostics): steps whose phi ran in two row
     // parts, host-model steps whose gradient read the update's pinned mirror,
     // speculative steps
@@ -523,7 +502,6 @@ EvPair take_pair(svgd_ctx *c)
     return p;
 }
 
-int64_t upper_pairs(int64_t n) { return n * (n - 1) / 2; }
 
 // diagnostic event kinds (svgd_set_timing level 2; svgd_get_diagnostics)
 enum { DG_PHI_KERNEL = 0, DG_PHI_WAIT = 1, DG_COLL = 2, DG_GATHER_G = 3 };
@@ -690,11 +668,6 @@ int allreduce_f64(svgd_ctx *c, double *buf, size_t cnt)
 
 // --------------------------------------------------------------- median --
 
-SelState make_state(int nsel, const uint64_t *ranks, uint64_t lo_key, uint64_t hi_key,
-                    int known_from = 63, uint64_t prefix = 0);
-
-// st_init (optional): the predicted bracket's select state, written by the
-// centring launch itself (no launch of its own)
 // Level 2: the start of the phi-wait span (run_phi) -- a pooled event of its
 // own, recorded where the median ends (the phase events go back to the pool
 // in svgd_get_timing; a diagnostic span must not share one of them)
@@ -711,6 +684,8 @@ int mark_median_end(svgd_ctx *c)
 // max |xc|^2 of the current X version (its parity slot)
 unsigned long long *nmax_cur(const svgd_ctx *c) { return c->nmax ? c->nmax + (c->xver & 1) : nullptr; }
 
+// st_init (optional): the predicted bracket's select state, written by the
+// centring launch itself (no launch of its own)
 int center(svgd_ctx *c, const SelState *st_init = nullptr)
 {
     // the fold (svgd_ctx::cpart): the previous version's partials as the centre
@@ -739,37 +714,10 @@ int center(svgd_ctx *c, const SelState *st_init = nullptr)
     return SVGD_OK;
 }
 
-// Upload a fresh select state from the host.  Bits >= known_from of every
-// selected key are already known to equal those of `prefix` (64: nothing
-// known; keys are < 2^63); the first digit is the RADIX_BITS below them.
-SelState make_state(int nsel, const uint64_t *ranks, uint64_t lo_key, uint64_t hi_key,
-                    int known_from, uint64_t prefix)
-{
-    SelState s{};
-    s.nsel = nsel;
-    s.rank[0] = ranks[0];
-    s.rank[1] = nsel > 1 ? ranks[1] : 0;
-    const uint64_t pm = known_from >= 64 ? 0ull : ~((1ull << known_from) - 1ull);
-    s.prefix[0] = s.prefix[1] = prefix & pm;
-    s.shift = known_from > RADIX_BITS ? known_from - RADIX_BITS : 0;
-    s.width = known_from > RADIX_BITS ? RADIX_BITS : known_from;
-    s.lo_key = lo_key;
-    s.hi_key = hi_key;
-    s.binv = (double)NBK / (double)(hi_key - lo_key);
-    return s;
-}
-
-int upload_state_s(svgd_ctx *c, const SelState &s)
+// A fresh select state (make_state) from the host to the device.
+int upload_state(svgd_ctx *c, const SelState &s)
 {
     HIPCHK(c, launch_set_state(s, c->st, c->stream));
-    return SVGD_OK;
-}
-
-int upload_state(svgd_ctx *c, int nsel, const uint64_t *ranks, uint64_t lo_key, uint64_t hi_key,
-                 int known_from = 63, uint64_t prefix = 0)
-{
-    HIPCHK(c, launch_set_state(make_state(nsel, ranks, lo_key, hi_key, known_from, prefix), c->st,
-                               c->stream));
     return SVGD_OK;
 }
 
@@ -799,150 +747,39 @@ constexpr double WIDE_SIGMA = 8.0; // re-bracket after a miss
 constexpr double MCOL_MAX_BAND = 0.02;
 
 SelState sample_state(svgd_ctx *c, double sigma);
-int sample_bracket(svgd_ctx *c, bool preset);
+int sample_bracket(svgd_ctx *c);
 int collect_counts(svgd_ctx *c);
 int median_finish_spec(svgd_ctx *c, double logn);
 
-double key_value(uint64_t k) { return __builtin_bit_cast(double, k); }
-
-// The next median D^2 from the last 2, 3 or 4: linear, quadratic (order 2:
-// on SVGD trajectories its errors are ~5x below the linear one's) or cubic
-// (order 3: through 4 points; on the bench trajectories another 2-5x below
-// the quadratic one's while the median still moves fast, noisier once it
-// settles -- profiles/r06_track_predictor.txt)
-double trk_extrapolate(const svgd_ctx *c, int order = 2)
-{
-    const double *m = c->trk_m;
-    double p = order >= 3 && c->trk_n >= 4 ? 4.0 * m[0] - 6.0 * m[1] + 4.0 * m[2] - m[3]
-               : c->trk_n >= 3          ? 3.0 * m[0] - 3.0 * m[1] + m[2]
-                                        : 2.0 * m[0] - m[1];
-    return p > 0.0 ? p : m[0];
-}
-
-// A resolved selection -> the tracking history: the selected lower key, the
-// error of the prediction the last steps implied, the bracket's density.
-void trk_record(svgd_ctx *c, uint64_t lo_key, uint64_t hi_key, uint64_t cand)
-{
-    const double m = key_value(c->h_trk[4]);
-    if (c->h_trk[6] || !(m > 0.0) || !std::isfinite(m)) {
-        c->trk_n = 0;
-        return;
-    }
-    // both extrapolations' errors (the ones this step's plan made, else from
-    // the same history)
-    if (c->trk_n >= 2) {
-        const double p = c->trk_pq >= 0 ? c->trk_pq : trk_extrapolate(c, 2);
-        c->trk_err[2] = c->trk_err[1];
-        c->trk_err[1] = c->trk_err[0];
-        c->trk_err[0] = std::fabs(m - p) / m;
-        c->trk_nerr = std::min(c->trk_nerr + 1, 3);
-    }
-    if (c->trk_n >= 4) {
-        const double p = c->trk_pc >= 0 ? c->trk_pc : trk_extrapolate(c, 3);
-        c->trk_errc[2] = c->trk_errc[1];
-        c->trk_errc[1] = c->trk_errc[0];
-        c->trk_errc[0] = std::fabs(m - p) / m;
-        c->trk_nerrc = std::min(c->trk_nerrc + 1, 3);
-    }
-    const double lo = key_value(lo_key);
-    const double hi = hi_key >= 0x7ff0000000000000ull ? INFINITY : key_value(hi_key);
-    c->trk_dens = (std::isfinite(hi) && hi > lo) ? (double)cand / (hi - lo) : 0.0;
-    // the averaged upper statistic: next to the lower one (1e-9 m at cfg3),
-    // or across a gap of the distance list (two equal clusters, even n)
-    const double m_hi = key_value(c->h_trk[5]);
-    c->trk_gap = m_hi > m && std::isfinite(m_hi) ? (m_hi - m) / m : 0.0;
-    c->trk_m[3] = c->trk_m[2];
-    c->trk_m[2] = c->trk_m[1];
-    c->trk_m[1] = c->trk_m[0];
-    c->trk_m[0] = m;
-    c->trk_n = std::min(c->trk_n + 1, 4);
-}
-
-// The predicted bracket for this step, or false (sample it): the predicted
-// band must not hold more candidates than the sampled bracket's would
-// (band_samp: its expected share of the pairs).  Of the quadratic and the
-// cubic extrapolation, the one whose half-width -- err_mult (cubic: twice
-// that) x the largest of its last 3 relative errors -- is narrower.
-bool trk_predict(svgd_ctx *c, double Mq, double band_samp, uint64_t *lo_key, uint64_t *hi_key,
-                 double *band_frac)
-{
-    if (!c->trk_allowed || c->trk_n < 2 || !(c->trk_dens > 0.0)) return false;
-    const double m1 = c->trk_m[0], m2 = c->trk_m[1];
-    c->trk_pq = trk_extrapolate(c, 2);
-    c->trk_pc = c->trk_n >= 4 ? trk_extrapolate(c, 3) : -1.0;
-    double e = 0.0;
-    if (c->trk_nerr == 0) e = std::fabs(m1 - m2) / m1; // no error seen yet: the drift itself
-    for (int k = 0; k < c->trk_nerr; ++k) e = std::max(e, c->trk_err[k]);
-    double wp = c->trk_err_mult * e, pred = c->trk_pq;
-    if (c->trk_pc >= 0 && c->trk_nerrc == 3) {
-        double ec = 0.0;
-        for (int k = 0; k < 3; ++k) ec = std::max(ec, c->trk_errc[k]);
-        if (2.0 * c->trk_err_mult * ec < wp) {
-            wp = 2.0 * c->trk_err_mult * ec;
-            pred = c->trk_pc;
-        }
-    }
-    const double w = std::max(wp, c->knobs.track_min_width.or_(2e-5)); // relative half-width floor
-    // the bracket has to hold both averaged statistics: the prediction follows
-    // the lower one, the upper one lay trk_gap above it.  Across a gap of the
-    // list (two equal clusters, even n: the largest distance inside a cluster
-    // and the smallest between the two) they move independently and no
-    // extrapolation of the lower one places the upper one -- a bracket around
-    // the lower one alone missed on every step, each redone: sample instead.
-    if (!(w < 0.05) || !(c->trk_gap < 0.05)) return false;
-    const double lo = pred * (1.0 - w), hi = pred * (1.0 + c->trk_gap) * (1.0 + w);
-    const double band = c->trk_dens * (hi - lo) / Mq;
-    if (!(band <= band_samp)) return false;
-    *lo_key = __builtin_bit_cast(uint64_t, lo);
-    *hi_key = __builtin_bit_cast(uint64_t, hi) + 1;
-    *band_frac = band;
-    c->trk_pred = pred;
-    return true;
-}
-
-// The default sample size of the bracket passes for M unordered pairs.
-int64_t sample_size(const svgd_ctx *c, int64_t M)
-{
-    // sample size: the band it leaves costs the collect pass, sampling and
-    // the two bracket passes cost ~S; measured optimum near M / 256 pairs
-    // (cfg2, M = 1.3e8: 2^19 -> median 0.222 vs 0.262 ms at 2^22), capped
-    // at 2^22 (cfg3, M = 2.1e9)
-    // tile path: whole random 64 x 64 tiles (MFMA Gram, ~1/1000 of the
-    // collect pass) instead of scattered pairs (2 random 8d-byte rows each).
-    // Its keys come in correlated 4096-key tiles, so it keeps 2^22 (1024
-    // tiles) whatever M: the bracket's sigma assumes many independent draws.
-    const bool tile_path = !c->rowpath && c->n / TB >= 2;
-    int64_t S = c->sample_size > 0 ? c->sample_size
-                : tile_path       ? int64_t(1) << 22
-                                  : std::min<int64_t>(std::max<int64_t>(M / 256, int64_t(1) << 18),
-                                                      int64_t(1) << 22);
-    const bool multi = c->comm || c->hcomm || c->sim_world > 1;
-    if (multi && !c->shard_sample && c->sample_size <= 0)
-        S = std::min<int64_t>(S, int64_t(1) << 20); // every rank draws all of it
-    return std::min<int64_t>(S, M);
-}
-
 // This step's bracket, decided before the centring launch (which then also
 // writes the predicted select state): predicted on speculative steps (row
-// and tile paths: keys are D^2 as doubles on both) when trk_predict allows
-// it, else sampled in median_begin.
+// and tile paths: keys are D^2 as doubles on both) when the tracker allows
+// it, else sampled in median_begin -- by the one sample plan both read.
 void trk_plan(svgd_ctx *c)
 {
     c->trk_go = false;
-    c->trk_pred = -1;
-    c->trk_pq = c->trk_pc = -1;
+    c->trk.begin_step();
     const int64_t M = upper_pairs(c->n);
-    if (!c->spec_step || c->sample_size > 0 || c->cand_capacity > 0 || M <= c->direct_max_pairs)
-        return;
-    const int64_t S = sample_size(c, M);
+    if (M <= c->direct_max_pairs) return; // every key is a candidate: no bracket
+    c->samp = plan_sample(M, !c->rowpath && c->n / TB >= 2, c->sample_size,
+                          c->comm || c->hcomm || c->sim_world > 1, c->shard_sample, c->sim_world,
+                          c->bracket_sigma);
+    if (!c->spec_step || c->sample_size > 0 || c->cand_capacity > 0) return;
     const double Mq = c->sim_world > 1 ? (double)c->sim_pairs : (double)M;
-    // the sampled bracket's expected share (sample_state at q = 1/2; whole-tile
-    // samples take 4x the sigmas, median_begin)
-    const bool tile_sample = !c->rowpath && c->n / TB >= 2 && S >= TB * TB;
-    const double sigma = tile_sample ? 4.0 * c->bracket_sigma : c->bracket_sigma;
-    const double sig = std::sqrt((double)S * 0.25) + 1.0;
-    const double band_samp = (2.0 * sigma * sig + 3.0) / (double)S;
-    c->trk_go = trk_predict(c, Mq, band_samp, &c->trk_lo, &c->trk_hi, &c->trk_band);
+    c->trk_go = c->trk.predict(Mq, c->samp.band_samp, &c->trk_lo, &c->trk_hi, &c->trk_band);
+}
+
+// The collect pass's candidate regions (and the compaction buffer beside
+// them) hold reg_cap keys each.
+int grow_regions(svgd_ctx *c)
+{
+    const int64_t need = c->reg_cap * c->nregions;
+    if (c->regions_alloc < need) {
+        CHK(dalloc(c, &c->regions, need));
+        CHK(dalloc(c, &c->cbuf, need));
+        c->regions_alloc = need;
+    }
+    return SVGD_OK;
 }
 
 // Phase 1 of the median: candidate bracket + collect pass + counts.
@@ -951,31 +788,9 @@ int median_begin(svgd_ctx *c)
 {
     c->trk_keys = false;
     const int64_t n = c->n;
-    int64_t rlo, rhi;
-    c->navg = svgd_plan_median_ranks(n, &rlo, &rhi);
-    if (c->sim_world > 1 && rlo >= 0) { // the same quantile of this rank's share of the pairs
-        const int64_t d = rhi - rlo;
-        rlo = (int64_t)((long double)rlo * (long double)c->sim_pairs / (long double)upper_pairs(n));
-        rhi = rlo + d;
-    }
-    // distinct non-negative upper ranks to select
-    c->nsel = 0;
-    c->src_lo = c->src_hi = -1;
-    if (rlo >= 0) {
-        c->sel_rank[c->nsel] = rlo;
-        c->src_lo = c->nsel++;
-    }
-    if (rhi >= 0) {
-        if (c->nsel == 1 && rhi == rlo) {
-            c->src_hi = 0;
-        } else {
-            c->sel_rank[c->nsel] = rhi;
-            c->src_hi = c->nsel++;
-        }
-    }
-    if (c->navg == 1) c->src_hi = c->src_lo;
+    c->sel = plan_ranks(n, c->sim_world, c->sim_pairs);
     c->median_pending = true;
-    if (c->nsel == 0) { // med = 0 (n <= 1 or all diagonal)
+    if (c->sel.nsel == 0) { // med = 0 (n <= 1 or all diagonal)
         c->med_path = SVGD_MEDIAN_DIRECT;
         return SVGD_OK;
     }
@@ -985,112 +800,75 @@ int median_begin(svgd_ctx *c)
     c->collect_grid = (int)std::max<int64_t>(1, std::min<int64_t>(tiles, c->collect_blocks));
     c->nregions = c->rowpath ? 4 * (int64_t)c->collect_grid : c->collect_grid;
     const int64_t tiles_per_blk = (tiles + c->nregions - 1) / c->nregions;
+    const int64_t pairs_own = tiles * c->pblock * c->pblock;
 
     if (M <= c->direct_max_pairs) {
         // every key is a candidate: bracket [0, ~0)
         c->med_path = SVGD_MEDIAN_DIRECT;
         c->reg_cap = tiles_per_blk * c->pblock * c->pblock;
         uint64_t z[2] = {0, 0};
-        CHK(upload_state(c, 1, z, 0, ~0ull));
+        CHK(upload_state(c, make_state(1, z, 0, ~0ull)));
+    } else if (c->trk_go) {
+        // predicted bracket (trk_plan; its select state was written by the
+        // centring launch): no sample, no radix passes (k_center zeroed the
+        // bucket counts); regions sized for 4x the band
+        c->med_path = SVGD_MEDIAN_BRACKET;
+        c->band_est = c->trk_band;
+        c->reg_cap = region_cap_predicted(c->trk_band, pairs_own, c->nregions);
     } else {
         c->med_path = SVGD_MEDIAN_BRACKET;
-        const bool tile_path = !c->rowpath && n / TB >= 2;
-        int64_t S = sample_size(c, M);
-        const double Mq = c->sim_world > 1 ? (double)c->sim_pairs : (double)M;
-        if (c->trk_go) {
-            // predicted bracket (trk_plan; its select state was written by
-            // the centring launch): no sample, no radix passes (k_center
-            // zeroed the bucket counts); regions sized for 4x the band
-            c->trk_steps += 1;
-            c->trk_band_sum += c->trk_band;
-            c->band_est = c->trk_band;
-            const int64_t pairs_own = tiles * c->pblock * c->pblock;
-            const int64_t total = (int64_t)(4.0 * c->trk_band * (double)pairs_own) + 2048 * c->nregions;
-            c->reg_cap = std::max<int64_t>(1, total / c->nregions);
-            const int64_t need = c->reg_cap * c->nregions;
-            if (c->regions_alloc < need) {
-                CHK(dalloc(c, &c->regions, need));
-                CHK(dalloc(c, &c->cbuf, need));
-                c->regions_alloc = need;
-            }
-            return collect_counts(c);
-        }
-        if (c->sim_world > 1 && c->shard_sample) S = std::max<int64_t>(1, S / c->sim_world); // a rank's share
-        const bool tile_sample = tile_path && S >= TB * TB;
-        if (tile_sample) S = S / (TB * TB) * (TB * TB);
+        SamplePlan &sp = c->samp;
+        const int64_t S = sp.S;
         if (c->sample_alloc < S) {
             CHK(dalloc(c, &c->sample_keys, S));
             c->sample_alloc = S;
         }
-        if (tile_sample)
+        if (sp.tile_sample)
             HIPCHK(c, launch_sample_tiles(c->plan.KP, c->xc, c->nrm, c->xcf, c->nrmf, c->XK, n,
                                           S / (TB * TB), c->sample_keys, c->stream));
         // sharded (P > 1, scattered pairs): rank r draws pairs [S r/P, S (r+1)/P)
         // of the one counter-based sequence and the bracket's histograms are
         // all-reduced -- the same sample, hence the same bracket, as on one rank
-        c->samp_shard = !tile_sample && (c->comm || c->hcomm) && c->shard_sample;
-        const int64_t g0 = c->samp_shard ? S * c->rank / c->world : 0;
-        c->samp_local = c->samp_shard ? S * (c->rank + 1) / c->world - g0 : S;
-        c->samp_S = S;
-        c->samp_qlo = (double)c->sel_rank[0] / Mq;
-        c->samp_qhi = (double)c->sel_rank[c->nsel - 1] / Mq;
-        // whole-tile samples are correlated (a far particle shifts its tile's
-        // 64 x 64 keys together): 3 sigma of S independent draws missed the
-        // bracket on ~40 % of cfg5 steps (each miss: a second collect pass);
-        // 12 measured none at no cost (the band stays ~1 % of the pairs)
-        const SelState init = sample_state(c, tile_sample ? 4.0 * c->bracket_sigma : c->bracket_sigma);
-        if (!tile_sample)
-            HIPCHK(c, launch_sample_keys(c->xc, c->nrm, c->xf, n, c->dim, c->plan.KP, g0, c->samp_local,
+        sp.shard = !sp.tile_sample && (c->comm || c->hcomm) && c->shard_sample;
+        const int64_t g0 = sp.shard ? S * c->rank / c->world : 0;
+        sp.local = sp.shard ? S * (c->rank + 1) / c->world - g0 : S;
+        const double Mq = c->sim_world > 1 ? (double)c->sim_pairs : (double)M;
+        sp.qlo = (double)c->sel.sel_rank[0] / Mq;
+        sp.qhi = (double)c->sel.sel_rank[c->sel.nsel - 1] / Mq;
+        const SelState init = sample_state(c, sp.sigma);
+        if (!sp.tile_sample)
+            HIPCHK(c, launch_sample_keys(c->xc, c->nrm, c->xf, n, c->dim, c->plan.KP, g0, sp.local,
                                          c->sample_keys, init, c->st, c->stream));
         else
             HIPCHK(c, launch_set_state(init, c->st, c->stream));
-        CHK(sample_bracket(c, true));
-        int64_t pairs_own = tiles * c->pblock * c->pblock;
-        int64_t total = c->cand_capacity;
-        if (total <= 0) {
-            const double frac = (c->samp_qhi - c->samp_qlo) + 16.0 / std::sqrt((double)S) + 0.004;
-            total = (int64_t)(2.0 * frac * (double)pairs_own) + 2048 * c->nregions;
-        }
-        c->reg_cap = std::max<int64_t>(1, total / c->nregions);
+        CHK(sample_bracket(c));
+        c->reg_cap = region_cap_sampled(sp, c->cand_capacity, pairs_own, c->nregions);
     }
-    const int64_t need = c->reg_cap * c->nregions;
-    if (c->regions_alloc < need) {
-        CHK(dalloc(c, &c->regions, need));
-        CHK(dalloc(c, &c->cbuf, need));
-        c->regions_alloc = need;
-    }
+    CHK(grow_regions(c));
     return collect_counts(c);
 }
 
-// Sample ranks bracketing the target quantiles (sigma sample-quantile standard
-// deviations either side): the select state of the bracket passes.
+// The select state of the bracket passes: the sample ranks sigma
+// sample-quantile standard deviations either side of the target quantiles.
 SelState sample_state(svgd_ctx *c, double sigma)
 {
-    const int64_t S = c->samp_S;
-    const double qlo = c->samp_qlo, qhi = c->samp_qhi;
-    const double sig_lo = std::sqrt((double)S * qlo * (1 - qlo)) + 1.0;
-    const double sig_hi = std::sqrt((double)S * qhi * (1 - qhi)) + 1.0;
-    double slo = std::floor(qlo * S - sigma * sig_lo) - 1;
-    double shi = std::ceil(qhi * S + sigma * sig_hi) + 1;
-    if (slo < 0) slo = 0;
-    if (shi > S - 1) shi = (double)(S - 1);
-    const uint64_t sr[2] = {(uint64_t)slo, (uint64_t)shi};
-    c->band_est = (shi - slo + 1.0) / (double)S; // expected share of pairs in the bracket
+    const SampleRanks r = sample_ranks(c->samp.S, c->samp.qlo, c->samp.qhi, sigma);
+    const uint64_t sr[2] = {r.slo, r.shi};
+    c->band_est = r.band_est;
     return make_state(2, sr, 0, ~0ull);
 }
 
-// The two radix passes over the sample from that state (already on the device
-// if preset: the sampler wrote it) -> bracket [lo_key, hi_key), which stays on
+// The two radix passes over the sample from that state (on the device: the
+// sampler or an upload wrote it) -> bracket [lo_key, hi_key), which stays on
 // the device (read by the collect pass).  Per pass: one histogram launch
 // (atomics into ghist), the all-reduce if the sample is sharded, one scan
 // launch; the last scan also sets the bracket.
-int sample_bracket(svgd_ctx *c, bool preset)
+int sample_bracket(svgd_ctx *c)
 {
-    (void)preset;
     for (int p = 0; p < 2; ++p) {
-        HIPCHK(c, launch_hist_regions(c->sample_keys, nullptr, 1, c->samp_local, 0, c->st, c->ghist,
+        HIPCHK(c, launch_hist_regions(c->sample_keys, nullptr, 1, c->samp.local, 0, c->st, c->ghist,
                                       c->stream));
-        if (c->samp_shard) CHK(allreduce_u64(c, c->ghist, 2 * RADIX));
+        if (c->samp.shard) CHK(allreduce_u64(c, c->ghist, 2 * RADIX));
         HIPCHK(c, launch_select_scan(c->st, c->ghist, p == 1, c->cnt3 + 3, c->stream));
     }
     return SVGD_OK;
@@ -1134,7 +912,8 @@ int median_finish_spec(svgd_ctx *c, double logn)
     // copy on the copy stream (a small copy there turned the X shard copies
     // into blit kernels competing with the median kernels)
     // (the compaction's blocks derive the bucket plan themselves: no plan launch)
-    const PlanArgs pa{c->cnt3, c->nsel, (uint64_t)c->sel_rank[0], (uint64_t)c->sel_rank[c->nsel - 1],
+    const RankPlan &r = c->sel;
+    const PlanArgs pa{c->cnt3, r.nsel, (uint64_t)r.sel_rank[0], (uint64_t)r.sel_rank[r.nsel - 1],
                       cap, c->d_status, c->h_status_dev,
                       c->sim_world > 1 ? 1 : 0, c->h_trk_dev};
     HIPCHK(c, launch_compact_buckets(c->regions, c->counts, c->nregions, c->reg_cap, c->st, seg, cap,
@@ -1150,7 +929,7 @@ int median_finish_spec(svgd_ctx *c, double logn)
     // step.)
     const bool by_seq = !c->timing && c->tlevel < 2;
     c->status_seq = by_seq ? ++c->seq_ctr : 0;
-    HIPCHK(c, launch_select_small(c->st, c->gseg, c->world, cap, c->navg, c->src_lo, c->src_hi, logn,
+    HIPCHK(c, launch_select_small(c->st, c->gseg, c->world, cap, r.navg, r.src_lo, r.src_hi, logn,
                                   c->scal, c->d_status, c->stream, c->h_trk_dev, c->status_seq));
     c->trk_keys = true;
     if (by_seq) {
@@ -1177,11 +956,11 @@ int median_finish(svgd_ctx *c)
     if (!c->median_pending) return fail(c, SVGD_ERR_RUNTIME, "[Runtime Error] median not begun.");
     c->median_pending = false;
     const double logn = std::log((double)c->n);
-    if (c->nsel == 0) {
+    if (c->sel.nsel == 0) {
         // every averaged order statistic is a diagonal zero
         uint64_t z[2] = {0, 0};
-        CHK(upload_state(c, 1, z, 0, 0));
-        HIPCHK(c, launch_finalize(c->st, c->navg, -1, -1, logn, c->scal, c->scal + 1, c->stream));
+        CHK(upload_state(c, make_state(1, z, 0, 0)));
+        HIPCHK(c, launch_finalize(c->st, c->sel.navg, -1, -1, logn, c->scal, c->scal + 1, c->stream));
         c->last_path = SVGD_MEDIAN_DIRECT;
         return SVGD_OK;
     }
@@ -1195,11 +974,11 @@ int median_finish(svgd_ctx *c)
     if (c->sim_world > 1 && !c->h_cnt[2] && c->h_cnt[1] > 0) {
         // measurement mode: the share is selected alone -- re-anchor the
         // ranks inside its candidates (the device plan does the same)
-        const int64_t dr = c->sel_rank[c->nsel - 1] - c->sel_rank[0];
-        c->sel_rank[0] = (int64_t)(c->h_cnt[0] + c->h_cnt[1] / 2);
-        if (c->nsel > 1) c->sel_rank[1] = c->sel_rank[0] + dr;
+        const int64_t dr = c->sel.sel_rank[c->sel.nsel - 1] - c->sel.sel_rank[0];
+        c->sel.sel_rank[0] = (int64_t)(c->h_cnt[0] + c->h_cnt[1] / 2);
+        if (c->sel.nsel > 1) c->sel.sel_rank[1] = c->sel.sel_rank[0] + dr;
     }
-    const uint64_t r0 = (uint64_t)c->sel_rank[0], r1 = (uint64_t)c->sel_rank[c->nsel - 1];
+    const uint64_t r0 = (uint64_t)c->sel.sel_rank[0], r1 = (uint64_t)c->sel.sel_rank[c->sel.nsel - 1];
     auto in_bracket = [&]() {
         return !c->h_cnt[2] && r0 >= c->h_cnt[0] && r1 < c->h_cnt[0] + c->h_cnt[1];
     };
@@ -1209,8 +988,8 @@ int median_finish(svgd_ctx *c)
         // ~2e-3 per step at the default 3 sigma): bracket again from the same
         // sample at WIDE_SIGMA and repeat the collect pass (one more pass)
         // instead of the streamed radix select (one pass per 11-bit digit)
-        CHK(upload_state_s(c, sample_state(c, std::max(c->bracket_sigma, WIDE_SIGMA))));
-        CHK(sample_bracket(c, false));
+        CHK(upload_state(c, sample_state(c, std::max(c->bracket_sigma, WIDE_SIGMA))));
+        CHK(sample_bracket(c));
         CHK(collect_counts(c));
         HIPCHK(c, hipEventSynchronize(c->ev_cnt));
         path = SVGD_MEDIAN_REBRACKET;
@@ -1220,12 +999,12 @@ int median_finish(svgd_ctx *c)
     bool ok = in_bracket();
     uint64_t ranks[2];
     if (ok) {
-        ranks[0] = c->sel_rank[0] - below;
-        ranks[1] = c->sel_rank[c->nsel - 1] - below;
+        ranks[0] = c->sel.sel_rank[0] - below;
+        ranks[1] = c->sel.sel_rank[c->sel.nsel - 1] - below;
     } else {
         path = SVGD_MEDIAN_FALLBACK;
-        ranks[0] = c->sel_rank[0];
-        ranks[1] = c->sel_rank[c->nsel - 1];
+        ranks[0] = c->sel.sel_rank[0];
+        ranks[1] = c->sel.sel_rank[c->sel.nsel - 1];
     }
     // Bucket select: the collect pass histogrammed the candidates in NBK
     // key-range buckets (all-reduced with the counts), so the bucket holding
@@ -1236,7 +1015,7 @@ int median_finish(svgd_ctx *c)
         const int64_t rr[2] = {(int64_t)ranks[0], (int64_t)ranks[1]};
         int bsel[2];
         int64_t rin[2], tot = 0;
-        const int ns = (c->nsel > 1 && ranks[1] != ranks[0]) ? 2 : 1;
+        const int ns = (c->sel.nsel > 1 && ranks[1] != ranks[0]) ? 2 : 1;
         if (svgd_plan_bucket_select(c->h_cnt + 3, NBK, ns, rr, bsel, rin, &tot) == 0 &&
             tot <= std::min<int64_t>(c->bucket_cap, CAPG)) {
             // one segment per rank, sized for the selected buckets' total (a
@@ -1244,14 +1023,14 @@ int median_finish(svgd_ctx *c)
             // rank, not the CAPG capacity
             const int64_t scap = std::max<int64_t>(1, tot);
             uint64_t *seg = c->gseg + (size_t)c->rank * (scap + 1);
-            HIPCHK(c, launch_set_sel(c->st, c->nsel, (uint64_t)rin[0],
-                                     (uint64_t)(c->nsel > 1 ? rin[ns - 1] : rin[0]), bsel[0],
+            HIPCHK(c, launch_set_sel(c->st, c->sel.nsel, (uint64_t)rin[0],
+                                     (uint64_t)(c->sel.nsel > 1 ? rin[ns - 1] : rin[0]), bsel[0],
                                      bsel[ns - 1], seg, c->stream));
             HIPCHK(c, launch_compact_buckets(c->regions, c->counts, c->nregions, c->reg_cap, c->st,
                                              seg, scap, nullptr, c->stream));
             CHK(allgather_u64(c, c->gseg, (size_t)scap + 1));
-            HIPCHK(c, launch_select_small(c->st, c->gseg, c->world, scap, c->navg, c->src_lo,
-                                          c->src_hi, logn, c->scal, nullptr, c->stream, c->h_trk_dev));
+            HIPCHK(c, launch_select_small(c->st, c->gseg, c->world, scap, c->sel.navg, c->sel.src_lo,
+                                          c->sel.src_hi, logn, c->scal, nullptr, c->stream, c->h_trk_dev));
             c->trk_keys = true;
             c->last_path = path;
             // the next step may take the device plan if this one would have
@@ -1263,14 +1042,10 @@ int median_finish(svgd_ctx *c)
     }
     // every candidate key lies in [lo_key, hi_key): their common leading bits
     // are known, so the radix passes start below them (bracket path only)
-    int known_from = 63;
-    if ((path == SVGD_MEDIAN_BRACKET || path == SVGD_MEDIAN_REBRACKET) && hi_key > lo_key) {
-        const uint64_t diff = lo_key ^ (hi_key - 1);
-        known_from = diff ? 64 - __builtin_clzll(diff) : 0;
-        if (known_from > 63) known_from = 63;
-    }
-    CHK(upload_state(c, c->nsel, ranks, 0, ~0ull, known_from, lo_key));
-    const int passes = (known_from + RADIX_BITS - 1) / RADIX_BITS;
+    const bool bracketed = path == SVGD_MEDIAN_BRACKET || path == SVGD_MEDIAN_REBRACKET;
+    const int known = bracketed ? known_from(lo_key, hi_key) : 63;
+    CHK(upload_state(c, make_state(c->sel.nsel, ranks, 0, ~0ull, known, lo_key)));
+    const int passes = (known + RADIX_BITS - 1) / RADIX_BITS;
     if (path == SVGD_MEDIAN_FALLBACK) {
         // streamed radix select over every pair (rare: the bracket missed)
         for (int p = 0; p < passes; ++p) {
@@ -1302,7 +1077,7 @@ int median_finish(svgd_ctx *c)
             }
         }
     }
-    HIPCHK(c, launch_finalize(c->st, c->navg, c->src_lo, c->src_hi, logn, c->scal, c->scal + 1,
+    HIPCHK(c, launch_finalize(c->st, c->sel.navg, c->sel.src_lo, c->sel.src_hi, logn, c->scal, c->scal + 1,
                               c->stream));
     c->last_path = path;
     return SVGD_OK;
@@ -1733,10 +1508,13 @@ int fetch_scale(svgd_ctx *c)
     return SVGD_OK;
 }
 
-// Check the pending speculative step; on a failed device plan restore X_t,
-// m_t, v_t, t and redo the step on the synchronous path (G_t is still on the
-// device).  Every rank sees the same status (it derives from all-reduced
-// counts), so the redo's collectives match across ranks.
+// A resolved selection (its keys and error flag in h_trk) and the bracket it
+// was taken from -> the tracking history.
+void trk_record(svgd_ctx *c, uint64_t lo_key, uint64_t hi_key, uint64_t cand)
+{
+    c->trk.record(c->h_trk[TRK_KEY0], c->h_trk[TRK_KEY1], c->h_trk[TRK_ERR], lo_key, hi_key, cand);
+}
+
 // A synchronous step's selection into the tracking history (its keys are in
 // h_trk once the step's scale is final; its bracket counts in h_cnt), or a
 // restart of the history when that step selected another way.
@@ -1745,8 +1523,8 @@ int trk_resolve_sync(svgd_ctx *c)
     const int s = c->trk_sync;
     c->trk_sync = 0;
     if (s == 0) return SVGD_OK;
-    if (s == 2 || !c->trk_allowed) {
-        c->trk_n = 0;
+    if (s == 2 || !c->trk.allowed) {
+        c->trk.restart();
         return SVGD_OK;
     }
     HIPCHK(c, hipEventSynchronize(c->ev_fin_use ? c->ev_fin_use : c->ev_fin));
@@ -1754,6 +1532,10 @@ int trk_resolve_sync(svgd_ctx *c)
     return SVGD_OK;
 }
 
+// Check the pending speculative step; on a failed device plan restore X_t,
+// m_t, v_t, t and redo the step on the synchronous path (G_t is still on the
+// device).  Every rank sees the same status (it derives from all-reduced
+// counts), so the redo's collectives match across ranks.
 int resolve_pending(svgd_ctx *c)
 {
     CHK(trk_resolve_sync(c));
@@ -1767,7 +1549,7 @@ int resolve_pending(svgd_ctx *c)
         // (it takes the runtime's locks the gradient worker's HIP calls need;
         // same-box A/B: equal at cfg3 / cfg2, cfg5 6.74-6.92 vs 6.78-7.77 ms
         // with the host gradient's spread 1.58-1.65 vs 1.60-1.97 ms)
-        volatile uint64_t *sq = c->h_trk + 8;
+        volatile uint64_t *sq = c->h_trk + TRK_SEQ;
         const auto t0 = std::chrono::steady_clock::now();
         auto t_idle = t0, t_query = t0;
         bool idle = false;
@@ -1796,11 +1578,11 @@ int resolve_pending(svgd_ctx *c)
         HIPCHK(c, hipEventSynchronize(c->ev_status_use ? c->ev_status_use : c->ev_status));
     }
     if (*c->h_status == 0) {
-        c->last_tot = (int64_t)c->h_trk[7];
-        if (c->trk_allowed) trk_record(c, c->h_trk[0], c->h_trk[1], c->h_trk[3]);
+        c->last_tot = (int64_t)c->h_trk[TRK_TOT];
+        if (c->trk.allowed) trk_record(c, c->h_trk[TRK_LO], c->h_trk[TRK_HI], c->h_trk[TRK_CAND]);
         return SVGD_OK;
     }
-    if (c->trk_pred >= 0) c->trk_miss += 1;
+    c->trk.failed();
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipStreamSynchronize(c->cstream));
     // this rank's rows of X_t, m_t, v_t back, then X_t all-gathered again
@@ -1827,12 +1609,9 @@ int resolve_pending(svgd_ctx *c)
 // Speculate this step's median when the last one would have allowed it.
 int plan_step(svgd_ctx *c)
 {
-    // the segment capacity: twice the last selection's keys, a power of two
-    // in [CAPR_MIN, CAPG] (a step whose buckets outgrow it fails its plan
-    // and is redone synchronously)
-    int64_t cap = CAPR_MIN;
-    while (cap < 2 * c->last_tot && cap < CAPG) cap <<= 1;
-    c->spec_cap = std::min<int64_t>(cap, CAPG);
+    // (a step whose buckets outgrow the segment capacity fails its plan and
+    // is redone synchronously)
+    c->spec_cap = spec_segment_cap(c->last_tot);
     c->spec_step = c->knobs.speculate.or_(1) && c->last_fast && c->scale_method == SVGD_SCALE_MEDIAN &&
                    c->bucket_cap >= c->spec_cap;
     if (c->spec_step && !c->bak) CHK(dalloc(c, &c->bak, 3 * std::max<int64_t>(1, c->nrows) * c->dim));
@@ -2121,13 +1900,14 @@ int alloc_median(svgd_ctx *c)
     CHK(dalloc(c, &c->ghist, 2 * RADIX));
     CHK(dalloc(c, &c->ccount, 1));
     CHK(dalloc(c, &c->d_status, 1));
-    c->trk_allowed = k.track_bracket.or_(c->trk_allowed);
+    c->trk.allowed = k.track_bracket.or_(c->trk.allowed);
+    c->trk.min_width = k.track_min_width.or_(c->trk.min_width);
     // A miss redoes the step; the band it saves is collect-pass work, which
     // outweighs the misses' cost only when the collect is large: 2.5 x the
     // recent error from N = 32768 up (cfg3: median phase 0.550 -> 0.513 ms,
     // 86 instead of 72 of 90 steps tracked, no miss in 360), 4 below (cfg2
     // at 2.5: 3 misses in 180 steps, slower) -- profiles/r04_track_mult_ab.txt
-    c->trk_err_mult = k.track_err_mult.or_(c->n >= 32768 ? 2.5 : 4.0);
+    c->trk.err_mult = k.track_err_mult.or_(c->n >= 32768 ? 2.5 : 4.0);
     return SVGD_OK;
 }
 
@@ -2154,8 +1934,8 @@ int alloc_host(svgd_ctx *c)
     HIPCHK(c, hipHostMalloc((void **)&c->h_status, sizeof(int), hipHostMallocCoherent));
     *c->h_status = 0;
     HIPCHK(c, hipHostGetDevicePointer((void **)&c->h_status_dev, c->h_status, 0));
-    HIPCHK(c, hipHostMalloc((void **)&c->h_trk, 16 * sizeof(uint64_t), hipHostMallocCoherent));
-    std::memset(c->h_trk, 0, 16 * sizeof(uint64_t));
+    HIPCHK(c, hipHostMalloc((void **)&c->h_trk, TRK_LEN * sizeof(uint64_t), hipHostMallocCoherent));
+    std::memset(c->h_trk, 0, TRK_LEN * sizeof(uint64_t));
     HIPCHK(c, hipHostGetDevicePointer((void **)&c->h_trk_dev, c->h_trk, 0));
     return SVGD_OK;
 }
@@ -2527,7 +2307,7 @@ int svgd_set_particles(svgd_ctx *c, const double *X)
     c->xh_valid = false;
     c->xver += 1;
     c->cpart_ver[0] = c->cpart_ver[1] = -1; // new particles: centred on their own mean
-    c->trk_n = c->trk_nerr = c->trk_nerrc = 0; // new particles: the median history restarts
+    c->trk.restart(true); // new particles: the median history restarts
     return SVGD_OK;
 }
 
@@ -3062,8 +2842,8 @@ int svgd_last_median_keys(svgd_ctx *c, double *sq_lo, double *sq_hi, int64_t *ra
         std::memcpy(&v, &s.prefix[src], sizeof(v));
         return v;
     };
-    if (sq_lo) *sq_lo = val(c->src_lo);
-    if (sq_hi) *sq_hi = val(c->src_hi);
+    if (sq_lo) *sq_lo = val(c->sel.src_lo);
+    if (sq_hi) *sq_hi = val(c->sel.src_hi);
     if (rank_lo) *rank_lo = rlo;
     if (rank_hi) *rank_hi = rhi;
     return SVGD_OK;
@@ -3111,21 +2891,21 @@ int svgd_get_diagnostics(svgd_ctx *c, double *out, int cap)
                                      c->h_wait_ms,
                                      (double)ranks,
                                      (double)c->host_threads,
-                                     (double)c->trk_steps,
-                                     (double)c->trk_miss,
+                                     (double)c->trk.steps,
+                                     (double)c->trk.miss,
                                      (double)c->sim_world,
                                      (double)c->cpu_quota,
                                      (double)c->n_split,
                                      (double)c->n_mirror,
                                      (double)c->n_spec,
                                      c->gcomm ? 1.0 : 0.0,
-                                     c->trk_band_sum};
+                                     c->trk.band_sum};
     for (int i = 0; i < cap && i < SVGD_DIAG_LEN; ++i) out[i] = v[i];
     for (int k = 0; k < 4; ++k) c->dg_ms[k] = 0, c->dg_cnt[k] = 0;
     c->h_grad_ms = c->h_xwait_ms = c->h_job_ms = c->h_wait_ms = 0;
     c->h_steps = 0;
-    c->trk_steps = c->trk_miss = 0;
-    c->trk_band_sum = 0;
+    c->trk.steps = c->trk.miss = 0;
+    c->trk.band_sum = 0;
     c->n_split = c->n_mirror = c->n_spec = 0;
     return cap < SVGD_DIAG_LEN ? cap : SVGD_DIAG_LEN;
 }

@@ -4,42 +4,9 @@
 #include <stdint.h>
 
 #include "built.h"
+#include "select_state.h"
 
 namespace svgd_amd {
-
-constexpr int RADIX_BITS = 11;
-constexpr int RADIX = 1 << RADIX_BITS;
-
-// Device-resident state of the (dual) radix select over 63-bit keys
-// (non-negative doubles as uint64).  Digits from the top: bits 62..52,
-// 51..41, 40..30, 29..19, 18..8, 7..0.
-struct SelState {
-    uint64_t prefix[2];   // resolved high bits of the two selected keys
-    uint64_t rank[2];     // remaining rank within the current prefix
-    uint64_t lo_key;      // candidate bracket [lo_key, hi_key)
-    uint64_t hi_key;
-    int32_t nsel;         // 1 or 2 active selections
-    int32_t shift;        // shift of the current digit
-    int32_t width;        // width of the current digit
-    int32_t pass;         // digits resolved so far
-    int32_t error;        // rank outside the histogram (should not happen)
-    int32_t pad_;
-    double binv;          // key-range buckets of [lo_key, hi_key): NBK / (hi - lo)
-    int32_t bsel[2];      // bucket of each selection (bucket select path)
-};
-
-// Key-range buckets of the candidate bracket: bucket(key) = floor((key - lo)
-// * binv), clamped to [0, NBK) -- monotone in the key, so buckets are
-// contiguous key ranges.  The collect pass histograms them, so one all-reduce
-// (counts + buckets) tells every rank which bucket holds each order statistic.
-constexpr int NBK = 2048;
-// per-rank capacity of the compacted selected-bucket keys (gathered over
-// ranks).  At cfg4 (N = 262144, 3.4e10 pairs) a sampled bracket's bucket
-// holds ~25k keys on one rank (2^22-pair sample) and ~100k at P > 1 (2^20):
-// 16384 sent every cfg4 step down the radix path, so it never speculated
-// and never tracked its bracket.  The synchronous path's all-gather moves
-// the step's own total, the speculative one the adaptive spec cap.
-constexpr int CAPG = 262144;
 
 // xc = X - mu (stride KP, zero padded), nrm = |xc|^2; nrm_in_slot also
 // stores |xc|^2 at xc[j*KP + d] (the row-stream median record).
@@ -155,9 +122,7 @@ hipError_t launch_hist_count(const uint64_t *keys, const unsigned long long *cco
 // zeroes bzero[0 .. NBK), the coming collect pass's bucket counts)
 hipError_t launch_select_scan(SelState *st, unsigned long long *ghist, int make_bracket,
                               unsigned long long *bzero, hipStream_t stream);
-// cnt = [below, candidates, overflowed regions, NBK bucket counts (zero without
-// bpart), lo_key, hi_key]: the first 3 + NBK entries are sums over ranks.
-constexpr int CNT_LO = 3 + NBK, CNT_HI = 4 + NBK, CNT_LEN = 5 + NBK;
+// cnt: CNT_LEN counters (select_state.h)
 hipError_t launch_counts_reduce(const unsigned long long *below, const uint32_t *counts,
                                 int64_t nblk, int64_t cap, const SelState *st,
                                 const uint32_t *bpart, int64_t nbpart,
@@ -185,8 +150,9 @@ struct PlanArgs {
     // SVGD_SIM_WORLD measurement mode: one rank's share is selected alone, so
     // r0 is re-anchored at the middle of its candidates (r1 keeps r1 - r0)
     int sim = 0;
-    // bracket tracking (optional, pinned host memory): [0] lo_key, [1] hi_key,
-    // [2] below, [3] candidates of this step's bracket (block 0 of the plan)
+    // bracket tracking (optional, pinned host memory, TrkSlot): this step's
+    // bracket, its below and candidate counts and the selected buckets' total
+    // (block 0 of the plan)
     uint64_t *trk = nullptr;
 };
 hipError_t launch_compact_buckets(const uint64_t *keys, const uint32_t *counts, int64_t nreg,
@@ -196,11 +162,11 @@ hipError_t launch_compact_buckets(const uint64_t *keys, const uint32_t *counts, 
 // exact selection of st->rank[s] within bucket st->bsel[s] over nseg gathered
 // segments [count, keys...] of stride seg_cap + 1 -> st->prefix[s] = that key,
 // then the scale as launch_finalize
-// trk (optional, pinned host memory): [4], [5] <- the selected keys, [6] <- error
+// trk (optional, pinned host memory): TRK_KEY0, TRK_KEY1 <- the selected keys, TRK_ERR <- error
 hipError_t launch_select_small(SelState *st, const uint64_t *segs, int nseg, int64_t seg_cap,
                                int navg, int src_lo, int src_hi, double logn, double *scal,
                                const int *status, hipStream_t stream, uint64_t *trk = nullptr,
-                               uint64_t seq = 0); // seq: stored into trk[8] at the end (spec steps)
+                               uint64_t seq = 0); // seq: stored into trk[TRK_SEQ] at the end (spec steps)
 // Device-side bucket plan from the all-reduced counts (speculative step): the
 // select state, seg[0] = 0 and *status = 0, or *status = 1 (bracket miss),
 // 2 (overflowed region), 3 (selected buckets hold > capr keys), also stored to
@@ -209,14 +175,6 @@ hipError_t launch_select_small(SelState *st, const uint64_t *segs, int nseg, int
 hipError_t launch_plan_select(const unsigned long long *cnt, SelState *st, int nsel, uint64_t r0,
                               uint64_t r1, int64_t capr, uint64_t *seg, int *status,
                               int *host_status, hipStream_t stream);
-// per-rank segment capacity of the speculative bucket select: adaptive
-// (svgd_capi.cpp plan_step: twice the last step's selected-bucket total,
-// rounded up to a power of two, within [CAPR_MIN, CAPG]); the all-gather
-// (P > 1) moves cap + 1 keys per rank.  At cfg3 a bucket holds ~3k keys:
-// a fixed 4096 made ~1 in 5 early steps fail the plan (each failure redoes
-// the step); the selection reads only the keys present.
-constexpr int CAPR_MIN = 4096;
-
 // Row-stream path (d <= 16): particle records rec_j = [xc_j | G_j - 2a xc_j | c_j | 0..],
 // stride phi_rec_stride(d) (built.h).  phi partials over S column splits ->
 // part[S][ldp][d+1].

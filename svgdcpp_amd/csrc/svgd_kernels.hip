@@ -1422,11 +1422,11 @@ __global__ __launch_bounds__(256) void k_compact_buckets(const uint64_t *__restr
         const PlanOut o = plan_block(pa.cnt, pa.nsel, pa.r0, pa.r1, pa.capr, pa.sim);
         if (blockIdx.x == 0 && threadIdx.x == 0) {
             if (pa.trk) { // this step's bracket and counts for the host's bracket tracking
-                pa.trk[0] = st->lo_key;
-                pa.trk[1] = st->hi_key;
-                pa.trk[2] = pa.cnt[0];
-                pa.trk[3] = pa.cnt[1];
-                pa.trk[7] = o.tot; // the selected buckets' keys (the next step's segment size)
+                pa.trk[TRK_LO] = st->lo_key;
+                pa.trk[TRK_HI] = st->hi_key;
+                pa.trk[TRK_BELOW] = pa.cnt[0];
+                pa.trk[TRK_CAND] = pa.cnt[1];
+                pa.trk[TRK_TOT] = o.tot; // the selected buckets' keys (the next step's segment size)
             }
             plan_publish(o, st, pa.nsel, pa.status, pa.host_status);
         }
@@ -1635,9 +1635,9 @@ __device__ __forceinline__ void select_small_body(SelState *st, const uint64_t *
                 if (nsel > 1) st->prefix[1] = sel[1];
                 finalize_scale(st, navg, src_lo, src_hi, logn, scal, scal + 1);
                 if (trk) {
-                    trk[4] = sel[0];
-                    trk[5] = nsel > 1 ? sel[1] : sel[0];
-                    trk[6] = ok ? 0 : 1;
+                    trk[TRK_KEY0] = sel[0];
+                    trk[TRK_KEY1] = nsel > 1 ? sel[1] : sel[0];
+                    trk[TRK_ERR] = ok ? 0 : 1;
                 }
             }
             return;
@@ -1755,14 +1755,14 @@ __device__ __forceinline__ void select_small_body(SelState *st, const uint64_t *
         if (nsel > 1) st->prefix[1] = prefix[1];
         finalize_scale(st, navg, src_lo, src_hi, logn, scal, scal + 1);
         if (trk) { // the selected keys for the host's bracket tracking
-            trk[4] = prefix[0];
-            trk[5] = nsel > 1 ? prefix[1] : prefix[0];
-            trk[6] = err ? 1 : 0;
+            trk[TRK_KEY0] = prefix[0];
+            trk[TRK_KEY1] = nsel > 1 ? prefix[1] : prefix[0];
+            trk[TRK_ERR] = err ? 1 : 0;
         }
     }
 }
 // seq (speculative steps at timing level 0): after the selection, thread 0
-// -- the one that wrote trk -- stores seq into trk[8], system-scope after its
+// -- the one that wrote trk -- stores seq into trk[TRK_SEQ], system-scope after its
 // other stores; the host polls it instead of an event between this kernel
 // and the next (an event record there cost a ~6 us dispatch gap per step).
 // The plan's status in pinned memory was stored by an earlier kernel.
@@ -1776,7 +1776,7 @@ __global__ __launch_bounds__(1024) void k_select_small(SelState *st, const uint6
     select_small_body(st, segs, nseg, seg_cap, navg, src_lo, src_hi, logn, scal, status, trk);
     if (seq && trk && threadIdx.x == 0) {
         __threadfence_system();
-        *reinterpret_cast<volatile uint64_t *>(trk + 8) = seq;
+        *reinterpret_cast<volatile uint64_t *>(trk + TRK_SEQ) = seq;
     }
 }
 

@@ -3,15 +3,18 @@
 Re-enacts, step after step, the sharded step protocol the library runs over
 RCCL (svgd_capi.cpp scale_begin / median_begin / collect_counts /
 median_finish(_spec) / upload_g_finish / run_phi_opt), with the
-library's own host planners (libsvgdcpp_amd.so) and numpy + the oracle as the
-arithmetic.  Per step:
+library's own host planners (libsvgdcpp_amd.so: the row and tile plans of
+plan.cpp and the median policy of median_plan.cpp -- the bracket tracker
+through its handle, the sample plan, the sample ranks, the speculative
+capacity -- so nothing of the policy is restated here) and numpy + the
+oracle as the arithmetic.  Per step:
 
   1. rows [row0, row1) = svgd_plan_rows; G for own rows;
   2. median (GaussianRBFKernel.hpp:164-188, 222-254), exact:
      a. bracket, decided before the collect (trk_plan):
         - tracked (the shipped default on speculative steps): the last
-          selected medians extrapolated quadratically, half-width 4x the
-          largest recent prediction error (trk_predict / trk_record); no
+          selected medians extrapolated, half-width a multiple of the largest
+          recent prediction error (svgd_plan_tracker_predict / _record); no
           sample, no collective;
         - else sampled: protocol "shipped" -- EVERY rank draws the whole
           sample (<= 2^20 pairs of one counter-based sequence) and runs the
@@ -39,7 +42,6 @@ Every collective is logged as (group, op); the test checks the sequence.
 """
 import ctypes
 import os
-import struct
 import sys
 import traceback
 
@@ -51,29 +53,9 @@ for p in (ROOT, os.path.join(ROOT, "oracle")):
         sys.path.insert(0, p)
 
 RADIX = 11
-NBK = 2048  # svgd_kernels.h
-CAPG = 262144  # svgd_kernels.h: the selected buckets' key cap of the bucket path
-CAPR_MIN = 4096  # svgd_kernels.h: the speculative cap's floor (plan_step: adaptive)
-
-
-def spec_cap(last_tot):
-    """svgd_capi.cpp plan_step: twice the last total, a power of two in [CAPR_MIN, CAPG]."""
-    cap = CAPR_MIN
-    while cap < 2 * last_tot and cap < CAPG:
-        cap <<= 1
-    return min(cap, CAPG)
+NBK = 2048  # select_state.h
+CAPG = 262144  # select_state.h: the selected buckets' key cap of the bucket path
 M64 = (1 << 64) - 1
-# svgd_capi.cpp tracked-bracket constants (trk_min_w, trk_err_mult)
-TRK_MIN_W = 2e-5
-TRK_ERR_MULT = 4.0
-
-
-def _key(x):
-    return struct.unpack("<Q", struct.pack("<d", x))[0]
-
-
-def _val(k):
-    return struct.unpack("<d", struct.pack("<Q", int(k)))[0]
 
 
 def _sqdist_keys(X, I, J, block):
@@ -108,14 +90,6 @@ def _sample_keys(X, g0, g1):
     j = np.where(j >= n, j - np.uint64(n), j)
     diff = X[i.astype(np.int64)] - X[j.astype(np.int64)]
     return np.einsum("ij,ij->i", diff, diff).view(np.uint64)
-
-
-def sample_size(M, world):
-    """svgd_capi.cpp sample_size(): automatic S, every rank draws all of it at P > 1."""
-    S = min(max(M // 256, 1 << 18), 1 << 22)
-    if world > 1:
-        S = min(S, 1 << 20)
-    return min(S, M)
 
 
 class Comms:
@@ -169,53 +143,35 @@ def _radix_select(reduce, keys, ranks, passes):
 
 
 class Tracker:
-    """svgd_capi.cpp trk_record / trk_extrapolate / trk_predict."""
+    """The library's bracket tracker (median_plan.cpp BracketTracker) through
+    its handle, with the creation defaults below N = 32768."""
 
-    def __init__(self):
-        self.m = [0.0, 0.0, 0.0]
-        self.n = 0
-        self.err = [0.0, 0.0, 0.0]
-        self.nerr = 0
-        self.dens = 0.0
-        self.pred = -1.0
+    def __init__(self, lib):
+        self.lib = lib
+        self.h = lib.svgd_plan_tracker_new(4.0, 2e-5)
+        assert self.h
 
-    def extrapolate(self):
-        m = self.m
-        p = 3.0 * m[0] - 3.0 * m[1] + m[2] if self.n >= 3 else 2.0 * m[0] - m[1]
-        return p if p > 0.0 else m[0]
+    def close(self):
+        self.lib.svgd_plan_tracker_free(self.h)
 
-    def record(self, m_sel, lo_key, hi_key, cand):
-        if not (m_sel > 0.0) or not np.isfinite(m_sel):
-            self.n = 0
-            return
-        if self.n >= 2:
-            p = self.pred if self.pred >= 0 else self.extrapolate()
-            self.err = [abs(m_sel - p) / m_sel] + self.err[:2]
-            self.nerr = min(self.nerr + 1, 3)
-        lo = _val(lo_key)
-        hi = np.inf if hi_key >= 0x7FF0000000000000 else _val(hi_key)
-        self.dens = cand / (hi - lo) if np.isfinite(hi) and hi > lo else 0.0
-        self.m = [m_sel] + self.m[:2]
-        self.n = min(self.n + 1, 3)
+    def begin_step(self):
+        self.lib.svgd_plan_tracker_begin_step(self.h)
 
     def predict(self, Mq, band_samp):
-        self.pred = -1.0
-        if self.n < 2 or not self.dens > 0.0:
+        lo, hi = ctypes.c_uint64(), ctypes.c_uint64()
+        band, pred, w = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+        if not self.lib.svgd_plan_tracker_predict(self.h, Mq, band_samp, ctypes.byref(lo), ctypes.byref(hi),
+                                                  ctypes.byref(band), ctypes.byref(pred), ctypes.byref(w)):
             return None
-        m1, m2 = self.m[0], self.m[1]
-        pred = self.extrapolate()
-        e = abs(m1 - m2) / m1 if self.nerr == 0 else 0.0
-        for k in range(self.nerr):
-            e = max(e, self.err[k])
-        w = max(TRK_ERR_MULT * e, TRK_MIN_W)
-        if not w < 0.05:
-            return None
-        lo, hi = pred * (1.0 - w), pred * (1.0 + w)
-        band = self.dens * (hi - lo) / Mq
-        if not band <= band_samp:
-            return None
-        self.pred = pred
-        return _key(lo), _key(hi) + 1
+        return lo.value, hi.value
+
+    def record(self, k_lo, k_hi, lo_key, hi_key, cand):
+        self.lib.svgd_plan_tracker_record(self.h, int(k_lo), int(k_hi), 0, int(lo_key), int(hi_key), int(cand))
+
+    def lost(self):
+        """A selection by another path left no keys: the history restarts
+        (trk_resolve_sync), as after a flagged record."""
+        self.lib.svgd_plan_tracker_record(self.h, 0, 0, 1, 0, 0, 0)
 
 
 def _bucket_of(keys, lo, binv):
@@ -226,7 +182,7 @@ def _bucket_of(keys, lo, binv):
 def _median(cm, lib, X, keys, protocol, sigma, shift, trk, spec, on_g, cap=CAPG):
     """One step's exact median; on_g() issues the G all-gather where
     upload_g_finish would.  Returns (med, path, bracket kind, selected D^2
-    of the lower order statistic, fast, bracket record for the tracker)."""
+    keys, fast, bracket record for the tracker)."""
     n = X.shape[0]
     world, rank = cm.dist.get_world_size(), cm.dist.get_rank()
     M = n * (n - 1) // 2
@@ -234,9 +190,11 @@ def _median(cm, lib, X, keys, protocol, sigma, shift, trk, spec, on_g, cap=CAPG)
     navg = lib.svgd_plan_median_ranks(n, ctypes.byref(lo_r), ctypes.byref(hi_r))
     sel = sorted({r for r in (lo_r.value, hi_r.value) if r >= 0})
     r0, r1 = sel[0], sel[-1]
-    S = sample_size(M, world)
-    sig = np.sqrt(S * 0.25) + 1.0
-    band_samp = (2.0 * sigma * sig + 3.0) / S
+    # the sample every rank would draw (scattered pairs) and its bracket's share
+    band_samp = ctypes.c_double()
+    S = lib.svgd_plan_median_sample(n, 0, 0, int(world > 1), int(protocol == "shard"), 1, sigma,
+                                    ctypes.byref(band_samp))
+    band_samp = band_samp.value
     # a. bracket: tracked (speculative steps only), else sampled
     br = trk.predict(float(M), band_samp) if (spec and protocol == "shipped" and not shift) else None
     kind = "tracked" if br is not None else "sampled"
@@ -250,9 +208,9 @@ def _median(cm, lib, X, keys, protocol, sigma, shift, trk, spec, on_g, cap=CAPG)
             g0, g1 = S * rank // world, S * (rank + 1) // world
             reduce = cm.allreduce
         skeys = _sample_keys(X, g0, g1)
-        qlo, qhi = r0 / M, r1 / M
-        slo = max(0.0, np.floor(qlo * S - sigma * (np.sqrt(S * qlo * (1 - qlo)) + 1)) - 1)
-        shi = min(S - 1.0, np.ceil(qhi * S + sigma * (np.sqrt(S * qhi * (1 - qhi)) + 1)) + 1)
+        slo, shi = ctypes.c_int64(), ctypes.c_int64()
+        lib.svgd_plan_sample_ranks(S, r0 / M, r1 / M, sigma, ctypes.byref(slo), ctypes.byref(shi), None)
+        slo, shi = float(slo.value), float(shi.value)
         if shift:  # tests: a bracket displaced off the median forces the fallback
             sh = shift * (np.sqrt(S * 0.25) + 1)
             slo, shi = min(S - 1.0, slo + sh), min(S - 1.0, shi + sh)
@@ -306,9 +264,8 @@ def _median(cm, lib, X, keys, protocol, sigma, shift, trk, spec, on_g, cap=CAPG)
         on_g()  # speculative step: every comm call of the median first
     out = [0.0 if kr < 0 else float(np.sqrt(np.uint64(vals[kr]).view(np.float64)))
            for kr in [lo_r.value, hi_r.value][:navg]]
-    m_sel = float(np.uint64(vals[r0]).view(np.float64))
-    rec = (lo, hi, cand_all) if path == "bracket" else None
-    return sum(out) / len(out), path, kind, m_sel, fast, rec, (tot.value if hit else 0)
+    rec = (int(vals[r0]), int(vals[r1]), lo, hi, cand_all) if path == "bracket" else None
+    return sum(out) / len(out), path, kind, fast, rec, (tot.value if hit else 0)
 
 
 def run(rank, world, port, n, d, block, q, sigma=3.0, shift=0.0, steps=1, protocol="shipped",
@@ -345,7 +302,7 @@ def run(rank, world, port, n, d, block, q, sigma=3.0, shift=0.0, steps=1, protoc
             tiles.append((I.value, J.value))
         opt = O.Adam((row1 - row0, d), lr, 0.9, 0.999)
         lower, upper = -np.full(d, bound), np.full(d, bound)
-        trk = Tracker()
+        trk = Tracker(lib)
         last_fast = False
         last_tot = 0
         hist = []
@@ -366,7 +323,9 @@ def run(rank, world, port, n, d, block, q, sigma=3.0, shift=0.0, steps=1, protoc
 
             # 2. the median: speculative when the last selection allowed it
             spec = last_fast
-            res = _median(cm, lib, X, keys, protocol, sigma, shift, trk, spec, on_g, spec_cap(last_tot))
+            trk.begin_step()
+            res = _median(cm, lib, X, keys, protocol, sigma, shift, trk, spec, on_g,
+                          lib.svgd_plan_spec_cap(last_tot))
             redo = res is None
             if redo:
                 # a failed device plan (resolve_pending): the speculative
@@ -375,13 +334,13 @@ def run(rank, world, port, n, d, block, q, sigma=3.0, shift=0.0, steps=1, protoc
                 # synchronously with a sampled bracket
                 gather_rows(X[row0:row1], what="X")
                 gather_rows(X[row0:row1], what="X_restore")
-                trk.pred = -1.0
+                trk.begin_step()
                 res = _median(cm, lib, X, keys, protocol, sigma, shift, trk, False, on_g)
-            med, path, kind, m_sel, fast, rec, last_tot = res
+            med, path, kind, fast, rec, last_tot = res
             if rec is not None:
-                trk.record(m_sel, *rec)
+                trk.record(*rec)
             else:
-                trk.n = 0
+                trk.lost()
             last_fast = fast
             a = np.log(n) / med ** 2
             # 4. phi_hat + Adam + clamp for own rows, X all-gathered
@@ -392,6 +351,7 @@ def run(rank, world, port, n, d, block, q, sigma=3.0, shift=0.0, steps=1, protoc
             hist.append(dict(X=Xt, X_new=X.copy(), G_all=box["G"], a=a, med=med, path=path,
                              bracket=kind, spec=spec, redo=redo, total=total,
                              colls=list(cm.log[mark:])))
+        trk.close()
         if rank == 0:
             q.put(("ok", dict(steps=hist, mus=mus, covs=covs, lr=lr, bound=bound)))
         dist.barrier()

@@ -1,5 +1,6 @@
 // Host-code sanitizer driver (AddressSanitizer + UndefinedBehaviorSanitizer):
-// the planner (plan.cpp, the phi plan included), the host Gaussian-sum models (host_models.cpp) and
+// the planners (plan.cpp, the phi plan included, and the median's host policy
+// median_plan.cpp), the host Gaussian-sum models (host_models.cpp) and
 // the CPU oracle (oracle/svgd_oracle.c, test infrastructure) built with
 // -fsanitize=address,undefined and exercised with cross-checks
 // (`make sanitize`, run by tests/test_sanitize.py).  The HIP-side host code
@@ -15,6 +16,7 @@
 
 #include "../../include/svgdcpp_amd/svgd_capi.h"
 #include "../../svgdcpp_amd/csrc/plan.h"
+#include "../../svgdcpp_amd/csrc/median_plan.h"
 
 extern "C" {
 void or_fill_splitmix(double *X, long count, double scale, uint64_t seed);
@@ -286,6 +288,136 @@ static void test_phi_plan()
     named.all_named();
 }
 
+static uint64_t key_of(double x) { return __builtin_bit_cast(uint64_t, x); }
+
+// The median's host policy (median_plan.cpp), at the edges of its arithmetic.
+static void test_median_plan()
+{
+    using namespace svgd_amd;
+    // the tracker through 0 .. 6 records of a smooth history: a prediction
+    // from the second record on, holding the next median
+    const double pairs = 1e8;
+    for (int nrec = 0; nrec <= 6; ++nrec) {
+        BracketTracker t;
+        double m = 4.0;
+        for (int k = 0; k < nrec; ++k, m *= 0.99) {
+            t.begin_step();
+            t.record(key_of(m), key_of(m), 0, key_of(0.99 * m), key_of(1.01 * m), 1000000);
+            CHECK(t.n == (k + 1 < 4 ? k + 1 : 4) && t.dens > 0 && t.gap == 0);
+        }
+        CHECK(t.nerr == (nrec >= 2 ? (nrec - 2 < 3 ? nrec - 2 : 3) : 0));
+        CHECK(t.nerrc == (nrec >= 4 ? nrec - 4 : 0));
+        uint64_t lo = 0, hi = 0;
+        double band = 0;
+        t.begin_step();
+        const bool go = t.predict(pairs, 1.0, &lo, &hi, &band);
+        CHECK(go == (nrec >= 2));
+        if (go) {
+            CHECK(lo <= key_of(m) && key_of(m) < hi && band > 0 && t.pred > 0 && t.width >= t.min_width);
+            CHECK(t.steps == 1 && t.band_sum == band);
+            t.failed();
+            CHECK(t.miss == 1);
+            // a non-finite or a flagged record: the medians are forgotten, the errors kept
+            const int nerr = t.nerr;
+            t.record(key_of(INFINITY), key_of(INFINITY), 0, lo, hi, 10);
+            CHECK(t.n == 0 && t.nerr == nerr);
+            CHECK(!t.predict(pairs, 1.0, &lo, &hi, &band));
+            t.record(key_of(m), key_of(m), 0, key_of(0.99 * m), key_of(1.01 * m), 10);
+            t.record(key_of(m), key_of(m), 1, key_of(0.99 * m), key_of(1.01 * m), 10);
+            CHECK(t.n == 0);
+            t.restart(true);
+            CHECK(t.nerr == 0 && t.nerrc == 0);
+        } else {
+            t.failed(); // (a sampled bracket's failure is no miss)
+            CHECK(t.miss == 0 && t.steps == 0);
+        }
+        // a bracket open to the infinity pattern (and beyond): no density, no prediction
+        for (uint64_t top : {0x7ff0000000000000ull, ~0ull}) {
+            t.record(key_of(m), key_of(m), 0, key_of(0.99 * m), top, 1000000);
+            CHECK(t.dens == 0);
+            t.begin_step();
+            CHECK(!t.predict(pairs, 1.0, &lo, &hi, &band));
+        }
+    }
+    // make_state at the edges of the known prefix
+    const uint64_t ranks[2] = {5, 9}, prefix = 0xfedcba9876543210ull;
+    for (int kf : {0, 11, 12, 63, 64}) {
+        const SelState s = make_state(2, ranks, 0, ~0ull, kf, prefix);
+        CHECK(s.nsel == 2 && s.rank[0] == 5 && s.rank[1] == 9);
+        CHECK(s.width == (kf > RADIX_BITS ? RADIX_BITS : kf) && s.shift == (kf > RADIX_BITS ? kf - RADIX_BITS : 0));
+        CHECK(s.shift + s.width == kf);
+        CHECK(s.prefix[0] == (kf >= 64 ? 0 : prefix >> kf << kf) && s.prefix[1] == s.prefix[0]);
+        CHECK(s.binv > 0);
+    }
+    CHECK(make_state(1, ranks, 0, 0).rank[1] == 0);
+    CHECK(known_from(0, 0) == 63 && known_from(8, 8) == 63 && known_from(8, 9) == 0);
+    CHECK(known_from(8, 10) == 1 && known_from(0, ~0ull) == 63 && known_from(0x4000, 0x4100) == 8);
+    // the rank plan: n = 0 .. 3 (diagonal zeros among the averaged), even and odd pair counts
+    for (int64_t n : {0, 1, 2, 3, 4, 5, 6, 7, 100, 101}) {
+        const RankPlan r = plan_ranks(n, 1, 0);
+        int64_t lo, hi;
+        CHECK(r.navg == svgd_plan_median_ranks(n, &lo, &hi));
+        CHECK(r.nsel >= 0 && r.nsel <= 2 && r.src_lo < r.nsel && r.src_hi < r.nsel);
+        CHECK((r.src_lo < 0) == (lo < 0) && (r.src_hi < 0) == (hi < 0));
+        if (r.src_lo >= 0) CHECK(r.sel_rank[r.src_lo] == lo);
+        if (r.src_hi >= 0) CHECK(r.sel_rank[r.src_hi] == hi);
+        if (r.nsel == 2) CHECK(r.sel_rank[0] < r.sel_rank[1]);
+        // (n = 0, an empty list, names rank 0 as svgd_plan_median_ranks does: no context has n < 1)
+        for (int q = 0; q < r.nsel && n > 0; ++q) CHECK(r.sel_rank[q] >= 0 && r.sel_rank[q] < upper_pairs(n));
+        if (n >= 4) { // one of 4 ranks' share: the same quantile (rounded down), the same spacing
+            const int64_t M = upper_pairs(n), Ms = M / 4;
+            const RankPlan q = plan_ranks(n, 4, Ms);
+            CHECK(q.nsel == r.nsel);
+            CHECK(q.sel_rank[0] * M <= r.sel_rank[0] * Ms && (q.sel_rank[0] + 1) * M > r.sel_rank[0] * Ms);
+            CHECK(q.sel_rank[q.nsel - 1] - q.sel_rank[0] == r.sel_rank[r.nsel - 1] - r.sel_rank[0]);
+        }
+    }
+    CHECK(plan_ranks(1, 1, 0).nsel == 0 && plan_ranks(1, 1, 0).src_lo == -1 && plan_ranks(1, 1, 0).src_hi == -1);
+    CHECK(plan_ranks(2, 1, 0).nsel == 1 && plan_ranks(3, 1, 0).nsel == 1 && plan_ranks(4, 1, 0).nsel == 2);
+    // the sample plan with fewer pairs than the sample (and the usual sizes)
+    for (bool tiles : {false, true})
+        for (int64_t M : {int64_t(1), int64_t(4095), int64_t(5000), int64_t(1) << 27, int64_t(1) << 31}) {
+            for (bool multi : {false, true}) {
+                const SamplePlan p = plan_sample(M, tiles, 0, multi, false, 1, 3.0);
+                CHECK(p.S >= 1 && p.S <= M && p.S <= (int64_t(1) << (multi ? 20 : 22)));
+                CHECK(p.tile_sample == (tiles && M >= 4096) && (!p.tile_sample || p.S % 4096 == 0));
+                CHECK(p.sigma == (p.tile_sample ? 12.0 : 3.0) && p.band_samp > 0);
+                const SampleRanks r = sample_ranks(p.S, 0.5, 0.5, p.sigma);
+                CHECK(r.slo <= r.shi && (int64_t)r.shi <= p.S - 1 && r.band_est > 0 && r.band_est <= 1.0);
+                if (!p.tile_sample && M >= (int64_t(1) << 27)) CHECK(std::fabs(r.band_est - p.band_samp) * p.S <= 2.0);
+                SamplePlan s = p;
+                s.qlo = s.qhi = 0.5;
+                CHECK(region_cap_sampled(s, 0, 1 << 20, 64) >= 2048 && region_cap_sampled(s, 10, 1 << 20, 64) == 1);
+            }
+            CHECK(plan_sample(M, tiles, 777, true, false, 1, 3.0).S == (M < 777 ? M : 777));
+            CHECK(plan_sample(M, tiles, 0, true, true, 4, 3.0).S >= 1);
+        }
+    CHECK(region_cap_predicted(0.0, 1 << 20, 64) == 2048 && region_cap_predicted(1e-3, 1 << 20, 1) == 4194 + 2048);
+    CHECK(spec_segment_cap(0) == CAPR_MIN && spec_segment_cap(2048) == 4096 && spec_segment_cap(2049) == 8192);
+    CHECK(spec_segment_cap(CAPG) == CAPG && spec_segment_cap(int64_t(1) << 40) == CAPG);
+    // the handle the Python tests drive
+    void *h = svgd_plan_tracker_new(4.0, 2e-5);
+    CHECK(h != nullptr);
+    uint64_t lo, hi;
+    double band, pred, width;
+    svgd_plan_tracker_begin_step(h);
+    CHECK(svgd_plan_tracker_predict(h, pairs, 1.0, &lo, &hi, &band, &pred, &width) == 0);
+    svgd_plan_tracker_record(h, key_of(2.0), key_of(2.0), 0, key_of(1.9), key_of(2.1), 1000);
+    svgd_plan_tracker_record(h, key_of(2.01), key_of(2.01), 0, key_of(1.9), key_of(2.1), 1000);
+    svgd_plan_tracker_begin_step(h);
+    CHECK(svgd_plan_tracker_predict(h, pairs, 1.0, &lo, &hi, &band, &pred, &width) == 1);
+    CHECK(pred == 2.0 * 2.01 - 2.0 && width > 0 && lo < hi);
+    svgd_plan_tracker_restart(h);
+    CHECK(svgd_plan_tracker_predict(h, pairs, 1.0, &lo, &hi, &band, &pred, &width) == 0);
+    svgd_plan_tracker_free(h);
+    double bs = 0;
+    int64_t a, b;
+    CHECK(svgd_plan_median_sample(3, 0, 0, 0, 0, 1, 3.0, &bs) == 3 && bs > 0);
+    svgd_plan_sample_ranks(3, 0.5, 0.5, 3.0, &a, &b, nullptr);
+    CHECK(a == 0 && b == 2);
+    CHECK(svgd_plan_spec_cap(5000) == 16384);
+}
+
 static void test_models_vs_oracle()
 {
     const int d = 5, k = 3;
@@ -345,6 +477,7 @@ int main()
 {
     test_plan();
     test_phi_plan();
+    test_median_plan();
     test_models_vs_oracle();
     test_oracle_paths();
     if (failures) {

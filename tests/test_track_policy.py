@@ -1,13 +1,21 @@
-"""The premise of the tracked median bracket (svgd_capi.cpp trk_predict):
-along an SVGD trajectory the median of D^2 moves smoothly enough that an
-extrapolation of the last selected medians -- the quadratic one (3 points,
+"""The tracked median bracket (median_plan.cpp BracketTracker) on the oracle's
+own trajectory: along an SVGD run the median of D^2 moves smoothly enough that
+an extrapolation of the last selected medians -- the quadratic one (3 points,
 half-width mult x the largest of its last three relative errors) or the cubic
 one (4 points, half-width 2 mult x its own), whichever half-width is narrower
--- contains the next median.  CPU only: the oracle's own trajectory
-(GaussianRBFKernel.hpp:164-188 median, SVGD.hpp:373-400 step, Adam), the
-policy restated in Python."""
+-- contains the next median.  CPU only: the oracle's trajectory
+(GaussianRBFKernel.hpp:164-188 median, SVGD.hpp:373-400 step, Adam) drives the
+library's tracker through its handle (svgd_plan_tracker_*: begin_step,
+predict, record per step, as a context does), and the policy restated in
+Python below stands beside it as the independent model: the two must agree on
+which steps are predicted and on every half-width."""
+import ctypes
+import struct
+
 import numpy as np
 import pytest
+
+from svgdcpp_amd import _capi as C
 
 
 def _extrap(h, order):
@@ -21,8 +29,9 @@ def _extrap(h, order):
 
 
 def _policy(m, mult=4.0, wmin=2e-5):
-    hist, eq, ec, used, miss, ws, cubic = [], [], [], 0, 0, [], 0
-    for mt in m:
+    """The model: (predicted steps, misses, half-widths, the steps' indices)."""
+    hist, eq, ec, used, miss, ws, at = [], [], [], 0, 0, [], []
+    for t, mt in enumerate(m):
         if len(hist) >= 2:
             pq = _extrap(hist, 2)
             pc = _extrap(hist, 3) if len(hist) >= 4 else None
@@ -30,7 +39,6 @@ def _policy(m, mult=4.0, wmin=2e-5):
             w, p = mult * e, pq
             if pc is not None and len(ec) >= 3 and 2 * mult * max(ec[-3:]) < w:
                 w, p = 2 * mult * max(ec[-3:]), pc
-                cubic += 1
             w = max(w, wmin)
             err = abs(mt - p) / mt
             eq.append(abs(mt - pq) / mt)
@@ -39,27 +47,118 @@ def _policy(m, mult=4.0, wmin=2e-5):
             if w < 0.05:
                 used += 1
                 ws.append(w)
+                at.append(t)
                 miss += err > w
         hist.append(mt)
-    return used, miss, ws
+    return used, miss, ws, at
+
+
+def _key(x):
+    return struct.unpack("<Q", struct.pack("<d", x))[0]
+
+
+def _val(k):
+    return struct.unpack("<d", struct.pack("<Q", k))[0]
+
+
+def _library(m, pairs, mult=4.0, wmin=2e-5, upper=1.0, band_samp=1.0):
+    """The library's tracker over the medians m (D^2): per step begin_step,
+    predict, record.  Each step records a bracket of 1 % of the median either
+    side holding 1 % of the pairs (the density a prediction needs; the band
+    of a prediction is then its half-width, under band_samp = 1), and `upper`
+    times the median as the upper order statistic.  Returns (predicted steps,
+    misses -- the recorded median or the upper statistic outside the returned
+    [lo, hi) --, half-widths, the steps' indices)."""
+    lib = C.lib()
+    t = lib.svgd_plan_tracker_new(mult, wmin)
+    assert t
+    used, miss, ws, at = 0, 0, [], []
+    lo, hi = ctypes.c_uint64(), ctypes.c_uint64()
+    band, pred, w = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+    try:
+        for step, mt in enumerate(m):
+            mt = float(mt)
+            lib.svgd_plan_tracker_begin_step(t)
+            if lib.svgd_plan_tracker_predict(t, float(pairs), band_samp, ctypes.byref(lo), ctypes.byref(hi),
+                                             ctypes.byref(band), ctypes.byref(pred), ctypes.byref(w)):
+                used += 1
+                ws.append(w.value)
+                at.append(step)
+                miss += not (lo.value <= _key(mt) and _key(mt * upper) < hi.value)
+                assert _val(lo.value) == pytest.approx(pred.value * (1.0 - w.value), rel=1e-14)
+            lib.svgd_plan_tracker_record(t, _key(mt), _key(mt * upper), 0, _key(0.99 * mt), _key(1.01 * mt),
+                                         int(0.01 * pairs))
+    finally:
+        lib.svgd_plan_tracker_free(t)
+    return used, miss, ws, at
+
+
+_CASES = [(4096, 8), (3000, 2)]
+_MEDS = {}
+
+
+def _meds(oracle, n, d):
+    """The squared medians of 40 oracle steps and the pair count (computed
+    once per case, shared by the tests below)."""
+    if (n, d) not in _MEDS:
+        X = oracle.splitmix((n, d), 3.0, 0x5EED)
+        mus = oracle.splitmix((4, d), 3.0, 0x5EEE)
+        covs = np.stack([np.eye(d) * (1.0 + 0.25 * q) for q in range(4)])
+        opt = oracle.Adam((n, d), 0.1, 0.9, 0.999)
+        out = []
+        for _ in range(40):
+            a, med = oracle.median_scale(X)
+            out.append(med * med)
+            G = oracle.logp_grad_gmm(X, mus, covs)
+            oracle.apply_update(X, opt.step(oracle.phi(X, G, a)))
+        _MEDS[(n, d)] = (np.array(out), n * (n - 1) // 2)
+    return _MEDS[(n, d)]
 
 
 # (the median of a small N has more step-to-step jitter: at N = 2048, d = 8
 # one of 37 predictions misses -- a redo, not an error; none at these sizes)
-@pytest.mark.parametrize("n,d", [(4096, 8), (3000, 2)])
+@pytest.mark.parametrize("n,d", _CASES)
 def test_tracked_bracket_policy_on_oracle_trajectory(oracle, n, d):
-    X = oracle.splitmix((n, d), 3.0, 0x5EED)
-    mus = oracle.splitmix((4, d), 3.0, 0x5EEE)
-    covs = np.stack([np.eye(d) * (1.0 + 0.25 * q) for q in range(4)])
-    opt = oracle.Adam((n, d), 0.1, 0.9, 0.999)
-    meds = []
-    for _ in range(40):
-        a, med = oracle.median_scale(X)
-        meds.append(med * med)
-        G = oracle.logp_grad_gmm(X, mus, covs)
-        oracle.apply_update(X, opt.step(oracle.phi(X, G, a)))
-    used, miss, ws = _policy(np.array(meds))
+    m, pairs = _meds(oracle, n, d)
+    used, miss, ws, at = _library(m, pairs)
+    print(f"library: predicted {used} missed {miss} median half-width {np.median(ws):.3g}")
     assert used >= 35
     assert miss == 0
     # narrow: the median half-width well under 1 % of the median
     assert np.median(ws) < 5e-3
+    # the model agrees: the same steps predicted, every half-width equal (the
+    # same half-dozen double operations on both sides: only a fused
+    # multiply-add could separate them, at ~1e-16; a change of policy moves a
+    # width by a factor of order one)
+    m_used, m_miss, m_ws, m_at = _policy(m)
+    assert (m_used, m_miss) == (used, miss)
+    assert m_at == at
+    np.testing.assert_allclose(ws, m_ws, rtol=1e-12, atol=0)
+
+
+@pytest.mark.parametrize("n,d", _CASES)
+def test_tracker_width_is_what_holds_the_median(oracle, n, d):
+    """No error multiple and a floor of 1e-14: every step from the third on is
+    predicted, and every bracket misses."""
+    m, pairs = _meds(oracle, n, d)
+    used, miss, _, _ = _library(m, pairs, mult=0.0, wmin=1e-14)
+    assert (used, miss) == (38, 38)
+
+
+@pytest.mark.parametrize("n,d", _CASES)
+def test_tracker_places_the_upper_statistic(oracle, n, d):
+    """The upper averaged statistic 4 % above the lower one: the bracket
+    reaches over it (as many predictions as without a gap, none missed);
+    6 % above -- a gap of the distance list -- the tracker stands down."""
+    m, pairs = _meds(oracle, n, d)
+    base = _library(m, pairs)
+    used, miss, _, at = _library(m, pairs, upper=1.04)
+    assert (used, miss, at) == (base[0], 0, base[3])
+    assert _library(m, pairs, upper=1.06)[0] == 0
+
+
+@pytest.mark.parametrize("n,d", _CASES)
+def test_tracker_yields_to_a_narrower_sample(oracle, n, d):
+    """A sampled bracket expected to hold 1e-12 of the pairs: no prediction."""
+    m, pairs = _meds(oracle, n, d)
+    assert _library(m, pairs, band_samp=1e-12)[0] == 0

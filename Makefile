@@ -1,16 +1,16 @@
 # Top-level build of the MI355X (gfx950) SVGD library and test/bench helpers.
 #   make            -> svgdcpp_amd/libsvgdcpp_amd.so (HIP kernels + C ABI, links RCCL)
 #   make oracle     -> oracle/liboracle.so (CPU restatement; test infrastructure)
-#   make cpp        -> build/{mvn_example,gmm_example,svgd_run_bench,test_api,test_dist,test_ksd,test_glm} (SVGDCpp-compatible C++ API)
+#   make cpp        -> build/{mvn_example,gmm_example,svgd_run_bench,test_api,test_dist,test_ksd,test_glm,test_glm_hess} (SVGDCpp-compatible C++ API)
 HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 HIPFLAGS ?= -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wall -Wno-unused-result
 SRC_DIR := svgdcpp_amd/csrc
 LIB := svgdcpp_amd/libsvgdcpp_amd.so
 OBJS := $(SRC_DIR)/svgd_kernels.o $(SRC_DIR)/svgd_collect.o $(SRC_DIR)/svgd_ksd.o $(SRC_DIR)/svgd_capi.o $(SRC_DIR)/plan.o $(SRC_DIR)/median_plan.o $(SRC_DIR)/host_models.o \
-        $(SRC_DIR)/hostcomm.o $(SRC_DIR)/svgd_glm.o $(SRC_DIR)/host_glm.o
+        $(SRC_DIR)/hostcomm.o $(SRC_DIR)/svgd_glm.o $(SRC_DIR)/svgd_gauss_hess.o $(SRC_DIR)/host_glm.o
 HDRS := $(SRC_DIR)/svgd_kernels.h $(SRC_DIR)/select_state.h $(SRC_DIR)/median_plan.h $(SRC_DIR)/built.h $(SRC_DIR)/dispatch.h $(SRC_DIR)/plan.h $(SRC_DIR)/svgd_ksd.h $(SRC_DIR)/svgd_device.h $(SRC_DIR)/svgd_exp_table.h \
-        $(SRC_DIR)/svgd_glm.h $(SRC_DIR)/host_glm.h include/svgdcpp_amd/svgd_capi.h
+        $(SRC_DIR)/svgd_glm.h $(SRC_DIR)/svgd_gauss_hess.h $(SRC_DIR)/host_glm.h include/svgdcpp_amd/svgd_capi.h
 
 all: $(LIB)
 
@@ -51,7 +51,7 @@ oracle:
 CPP_FLAGS := -O2 -std=c++17 -Wall -fopenmp -Iinclude
 CPP_LINK := -Lsvgdcpp_amd -lsvgdcpp_amd -Wl,-rpath,'$$ORIGIN/../svgdcpp_amd' -Wl,--allow-shlib-undefined
 CPP_HDRS := $(wildcard include/SVGDCpp/*.hpp include/SVGDCpp/*/*.hpp) include/Core include/Model include/Kernel include/Optimizer
-CPP_BINS := build/mvn_example build/gmm_example build/svgd_run_bench build/test_api build/test_dist build/test_ksd build/test_glm
+CPP_BINS := build/mvn_example build/gmm_example build/svgd_run_bench build/test_api build/test_dist build/test_ksd build/test_glm build/test_glm_hess
 
 cpp: $(CPP_BINS) build/host_grad_bench
 
@@ -77,6 +77,10 @@ build/test_ksd: tests/cpp/test_ksd.cpp $(CPP_HDRS) $(LIB)
 	$(CXX) $(CPP_FLAGS) $< -o $@ $(CPP_LINK)
 
 build/test_glm: tests/cpp/test_glm.cpp $(CPP_HDRS) $(LIB)
+	@mkdir -p build
+	$(CXX) $(CPP_FLAGS) $< -o $@ $(CPP_LINK)
+
+build/test_glm_hess: tests/cpp/test_glm_hess.cpp $(CPP_HDRS) $(LIB)
 	@mkdir -p build
 	$(CXX) $(CPP_FLAGS) $< -o $@ $(CPP_LINK)
 

@@ -333,8 +333,10 @@ public:
     /** True when Step() runs wholly on the device, grad log p included
      *  (svgd_step(ctx, NULL) with the model mirrored by svgd_set_device_glm):
      *  a model of exactly the GeneralizedLinearModel type (a subclass keeps
-     *  the split calls), the Median or Constant scale, no matrix logging
-     *  (which reads X_t and G from the host buffers). */
+     *  the split calls), any scale method -- the Hessian scale only when the
+     *  kernel's target model is the stepped model, whose device mirror then
+     *  supplies the Hessian sum too (svgd_set_device_hessian) -- and no matrix
+     *  logging (which reads X_t and G from the host buffers). */
     bool UsesDeviceModelStep() const
     {
         if (!UsesDevicePath() || log_intermediate_matrices_)
@@ -342,7 +344,8 @@ public:
         const Model &m = *model_ptr_;
         if (typeid(m) != typeid(GeneralizedLinearModel))
             return false;
-        return rbf_ptr_->GetScaleMethod() != GaussianRBFKernel::ScaleMethod::Hessian;
+        return rbf_ptr_->GetScaleMethod() != GaussianRBFKernel::ScaleMethod::Hessian ||
+               rbf_ptr_->GetTargetModel() == model_ptr_;
     }
 
     /** Rows [row0, row1) of the particles this rank steps (all of them on one GPU). */
@@ -520,6 +523,9 @@ protected:
             device_m0_ = glm.BatchBegin();
             device_count_ = glm.BatchCount();
         }
+        // a Hessian scale on the device step: the device model supplies the sum
+        Check(svgd_set_device_hessian(
+            c, UsesDeviceModelStep() && rbf_ptr_->GetScaleMethod() == GaussianRBFKernel::ScaleMethod::Hessian));
     }
 
     void ConfigureScale()

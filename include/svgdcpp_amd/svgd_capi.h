@@ -343,6 +343,24 @@ int svgd_set_device_glm(svgd_ctx *ctx, const void *glm);
 /* Move the device GLM's batch window (no data is copied); SVGD_ERR_UNSET
  * without a device GLM, SVGD_ERR_ARG for a window outside the data. */
 int svgd_set_device_glm_batch(svgd_ctx *ctx, int64_t m0, int64_t count);
+/* H_shard_out (dim x dim, row-major) = sum_i -hess log p(x_i) of the device
+ * model (either kind) over this rank's rows of the current particles: what
+ * svgd_glm_neg_hess_sum / svgd_model_neg_hess_sum return for those rows,
+ * computed on the device in fp64 whatever the context's dtype.  An empty
+ * shard gives zeros; a GLM's result is exactly symmetric; two calls on the
+ * same state return the same bits.  An observer like svgd_device_logp_grad.
+ * SVGD_ERR_UNSET without a device model, SVGD_ERR_ARG for NULL. */
+int svgd_device_neg_hess_sum(svgd_ctx *ctx, double *H_shard_out);
+/* on != 0: under SVGD_SCALE_HESSIAN, svgd_step(ctx, NULL) takes the step's
+ * Hessian sum from the device model -- the sum above, computed straight into
+ * the scale's source and summed over the ranks where
+ * svgd_set_step_hessian_sum would do it, with no host copy; every rank must
+ * set the switch alike.  A sum supplied for the step with
+ * svgd_set_step_hessian_sum wins (a kernel whose target model is not the
+ * stepped one).  Off (the default): that step fails with the Unset Error, as
+ * before.  Harmless under the other scale methods; svgd_set_device_model and
+ * svgd_set_device_glm leave the switch alone. */
+int svgd_set_device_hessian(svgd_ctx *ctx, int on);
 
 /* Kernelized Stein discrepancy of the current particles with the isotropic
  * RBF kernel k = exp(-a |x - y|^2), whatever scale method the context steps

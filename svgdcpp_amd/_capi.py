@@ -132,6 +132,8 @@ SIGNATURES = {
     "svgd_glm_neg_hess_sum": (ctypes.c_int, [_P, _D, _I64, _D]),
     "svgd_set_device_glm": (ctypes.c_int, [_P, _P]),
     "svgd_set_device_glm_batch": (ctypes.c_int, [_P, _I64, _I64]),
+    "svgd_device_neg_hess_sum": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double)]),
+    "svgd_set_device_hessian": (ctypes.c_int, [_P, ctypes.c_int]),
 }
 
 _lib = None

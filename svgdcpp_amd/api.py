@@ -943,6 +943,18 @@ class Context:
         self.check(self.lib.svgd_device_logp_grad(self.h, C.dptr(out)))
         return out
 
+    def device_neg_hess_sum(self):
+        """This rank's Σᵢ −∇²log p(xᵢ) of the device model at the current
+        particles (svgd_device_neg_hess_sum), (d, d)."""
+        out = np.empty((self.dim, self.dim), dtype=np.float64)
+        self.check(self.lib.svgd_device_neg_hess_sum(self.h, C.dptr(out)))
+        return out
+
+    def set_device_hessian(self, on):
+        """Under the Hessian scale, step_device() takes the step's Hessian sum
+        from the device model (svgd_set_device_hessian); every rank alike."""
+        self.check(self.lib.svgd_set_device_hessian(self.h, int(bool(on))))
+
     def step_device(self):
         self.check(self.lib.svgd_step(self.h, None))
 
@@ -1074,15 +1086,21 @@ class SVGD:
         if self.UsesDeviceModelStep():
             c.set_device_model(self.model_)
             self._device_batch = self.model_.batch_
+        # a Hessian scale on the device step: the device model supplies the sum
+        c.set_device_hessian(self.UsesDeviceModelStep()
+                             and k.scale_method_ == GaussianRBFKernel.ScaleMethod.Hessian)
         self._initialized = True
 
     def UsesDeviceModelStep(self):
         """The whole step, grad log p included, runs on the device
         (svgd_step(ctx, NULL)): a model of exactly the built-in GLM type, an
-        RBF kernel on the device path with a Median or Constant scale, and no
+        RBF kernel on the device path -- with a Hessian scale only when the
+        kernel's target model is the stepped model, whose device mirror then
+        supplies the Hessian sum too (svgd_set_device_hessian) -- and no
         matrix logging (which reads X_t and G from the host buffers)."""
+        hess = self.kernel_.scale_method_ == GaussianRBFKernel.ScaleMethod.Hessian
         return (self.ctx is not None and type(self.model_) is GeneralizedLinearModel
-                and self.kernel_.scale_method_ != GaussianRBFKernel.ScaleMethod.Hessian
+                and (not hess or self.kernel_.target_model_ is self.model_)
                 and not self.log_)
 
     def Run(self):

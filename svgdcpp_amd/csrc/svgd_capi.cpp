@@ -32,6 +32,7 @@
 #include "median_plan.h"
 #include "svgd_ksd.h"
 #include "svgd_glm.h"
+#include "svgd_gauss_hess.h"
 #include "hostcomm.h"
 #include "host_models.h"
 #include "host_glm.h"
@@ -176,6 +177,16 @@ struct svgd_ctx {
         int smax = 1;                 // data splits that fill the device at most twice
         int64_t ldp = 0;
     } glm;
+    // device Hessian sum of the device model (svgd_device_neg_hess_sum, and
+    // the Hessian-scale step's when `on`: svgd_set_device_hessian)
+    struct Hess {
+        bool on = false;
+        int64_t resident = 1;     // work-group slots of the GLM weight pass
+        double *wpart = nullptr;  // GLM: per-split weight sums
+        double *W = nullptr;      // GLM: W_m of the window
+        double *part = nullptr;   // per-block d x d (GLM: triangle) partial sums
+        double *out = nullptr;    // d x d, the observer's result
+    } hess;
     int64_t row0 = 0, row1 = 0, nrows = 0, chunk = 0;
     Knobs knobs;  // the environment, read once at creation (read_knobs)
     PhiPlan plan; // the phi kernel of this context and its launch parameters (plan_phi)
@@ -2103,6 +2114,7 @@ int svgd_destroy(svgd_ctx *c)
                        c->part,  c->dm_mu, c->dm_prec, c->sc_src, c->sc_M, c->sc_L, c->wv, c->zc,
                        c->sc_sgn,  c->sc_work, c->bak, c->srec, c->rowpart, c->colpart, c->contrib,
                        c->xrecv_buf, c->tab8k, c->glm.rec, c->glm.part,
+                       c->hess.wpart, c->hess.W, c->hess.part, c->hess.out,
                        c->ksd.G, c->ksd.mu, c->ksd.mpart, c->ksd.rec, c->ksd.xt, c->ksd.vt, c->ksd.nrm,
                        c->ksd.cvec, c->ksd.diag, c->ksd.part, c->ksd.rows, c->ksd.bpart, c->ksd.out};
     float *fbufs[] = {c->xcf, c->nrmf, c->cvf, c->Vf, c->zcf, c->XS, c->VS};
@@ -2570,6 +2582,36 @@ int launch_device_model_grad(svgd_ctx *c, const double *X, int64_t rows, double 
     return SVGD_OK;
 }
 
+// sum_i -hess log p(x_i) of the device model over `rows` particles X (stride
+// d) -> H (d x d, device), fp64, on the context's stream; rows == 0: zeros
+int launch_device_model_hess(svgd_ctx *c, const double *X, int64_t rows, double *H)
+{
+    const int d = c->dim;
+    if (c->glm.m > 0) {
+        const svgd_ctx::Glm &g = c->glm;
+        if (rows <= 0) {
+            HIPCHK(c, hipMemsetAsync(H, 0, sizeof(double) * (size_t)d * d, c->stream));
+            return SVGD_OK;
+        }
+        const bool logistic = g.link == SVGD_GLM_LOGISTIC;
+        if (logistic) {
+            // particle splits: record groups x S fills the resident slots at
+            // most twice (as svgd_set_device_glm sizes the score's splits)
+            const int64_t groups = glm_wgroups(g.count);
+            const int S = (int)std::min<int64_t>(std::max<int64_t>(1, 2 * c->hess.resident / groups),
+                                                 glm_tiles(rows));
+            HIPCHK(c, launch_glm_weights(d, X, rows, g.rec, g.m0, g.count, S, c->hess.wpart, c->hess.W,
+                                         c->stream));
+        }
+        HIPCHK(c, launch_glm_wgram(d, g.rec, g.m0, g.count, logistic ? c->hess.W : nullptr, (double)rows,
+                                   g.lik_scale * ((double)g.m / (double)g.count),
+                                   g.prior_prec * (double)rows, c->hess.part, H, c->stream));
+        return SVGD_OK;
+    }
+    HIPCHK(c, launch_gauss_hess_sum(X, rows, d, c->dm_k, c->dm_mu, c->dm_prec, c->hess.part, H, c->stream));
+    return SVGD_OK;
+}
+
 } // namespace
 
 int svgd_step(svgd_ctx *c, const double *G_shard)
@@ -2584,6 +2626,13 @@ int svgd_step(svgd_ctx *c, const double *G_shard)
         return fail(c, SVGD_ERR_ARG,
                     "[Argument Error] Null log-gradient buffer and no device model set.");
     CHK(svgd_begin_step(c, nullptr));
+    if (c->scale_method == SVGD_SCALE_HESSIAN && c->hess.on && !c->hess_ready) {
+        // the device model's Hessian sum, where svgd_set_step_hessian_sum
+        // would upload the caller's (a sum supplied for this step wins)
+        CHK(launch_device_model_hess(c, c->X + (size_t)c->row0 * c->dim, c->nrows, c->sc_src));
+        CHK(allreduce_f64(c, c->sc_src, (size_t)c->dim * c->dim));
+        c->hess_ready = true;
+    }
     CHK(launch_device_model_grad(c, c->X + (size_t)c->row0 * c->dim, c->nrows,
                                  c->G + (size_t)c->row0 * c->dim));
     c->mark = nullptr; // (the gradient kernel runs after the median's end event)
@@ -2612,6 +2661,9 @@ int svgd_set_device_model(svgd_ctx *c, const void *model)
                              hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->dm_prec, m->prec.data(), sizeof(double) * m->prec.size(),
                              hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    CHK(dalloc(c, &c->hess.part, (int64_t)gauss_hess_grid(c->nrows) * m->d * m->d));
+    CHK(dalloc(c, &c->hess.out, (int64_t)m->d * m->d));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->dm_k = m->k;
     c->glm.m = 0; // the two device models exclude each other
@@ -2658,6 +2710,14 @@ int svgd_set_device_glm(svgd_ctx *c, const void *glm)
     g.ldp = std::max<int64_t>(1, c->nrows);
     CHK(dalloc(c, &g.rec, (int64_t)rec.size()));
     CHK(dalloc(c, &g.part, (int64_t)g.smax * g.ldp * d));
+    // the Hessian sum's work areas, for any window of these data: the weight
+    // pass launches record groups x S <= max(2 resident, groups) work-groups
+    c->hess.resident = (int64_t)std::max(1, cus) * glm_wpass_blocks_per_cu(d);
+    CHK(dalloc(c, &c->hess.wpart,
+               std::max<int64_t>(2 * c->hess.resident, glm_wgroups(m->m)) * GLM_ROWS_PER_WG));
+    CHK(dalloc(c, &c->hess.W, glm_wgroups(m->m) * GLM_ROWS_PER_WG));
+    CHK(dalloc(c, &c->hess.part, (int64_t)glm_gram_grid(m->m) * (d * (d + 1) / 2)));
+    CHK(dalloc(c, &c->hess.out, (int64_t)d * d));
     HIPCHK(c, hipMemcpyAsync(g.rec, rec.data(), sizeof(double) * rec.size(), hipMemcpyHostToDevice,
                              c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2693,6 +2753,30 @@ int svgd_device_logp_grad(svgd_ctx *c, double *G_shard_out)
     HIPCHK(c, hipMemcpyAsync(G_shard_out, c->phi, sizeof(double) * (size_t)c->nrows * c->dim,
                              hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SVGD_OK;
+}
+
+int svgd_device_neg_hess_sum(svgd_ctx *c, double *H_shard_out)
+{
+    CHK(check_ready(c));
+    CHK(resolve_pending(c));
+    if (!has_device_model(c)) return fail(c, SVGD_ERR_UNSET, "[Unset Error] No device model set.");
+    if (!H_shard_out) return fail(c, SVGD_ERR_ARG, "[Argument Error] Null output buffer.");
+    HIPCHK(c, hipSetDevice(c->device));
+    // work is queued behind the step's marks: they no longer end the stream
+    c->mark = c->phi_end = c->last_phi_end = nullptr;
+    CHK(launch_device_model_hess(c, c->X + (size_t)c->row0 * c->dim, c->nrows, c->hess.out));
+    HIPCHK(c, hipMemcpyAsync(H_shard_out, c->hess.out, sizeof(double) * (size_t)c->dim * c->dim,
+                             hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SVGD_OK;
+}
+
+int svgd_set_device_hessian(svgd_ctx *c, int on)
+{
+    if (!c) return SVGD_ERR_ARG;
+    CHK(resolve_pending(c));
+    c->hess.on = on != 0;
     return SVGD_OK;
 }
 

@@ -50,4 +50,38 @@ hipError_t launch_glm_finish(int d, const double *X, int64_t nrows, const double
                              int64_t ldp, double scale, double lambda, double *G,
                              hipStream_t stream);
 
+// ---- Hessian sum: -sum_i hess log p(theta_i) over `nrows` particles
+//   H = scale sum_{m in window} W_m a_m a_m^T + lambda nrows I
+//   W_m = sum_i w(a_m . theta_i), w = e / (1 + e)^2, e = exp(-|z|)  (logistic)
+//   W_m = nrows                                                     (Gaussian link)
+constexpr int GLM_GRAM_THREADS = 256;
+constexpr int GLM_GRAM_BLOCK = 64;    // records per block of the weighted Gram
+constexpr int GLM_GRAM_CHUNK = 64;    // records in LDS at a time
+constexpr int GLM_GRAM_MAXGRID = 512; // work-groups, each a contiguous range of blocks
+constexpr int GLM_GRAM_EPT = (64 * 65 / 2 + GLM_GRAM_THREADS - 1) / GLM_GRAM_THREADS; // triangle elements per thread
+
+// record groups of the weight pass (one work-group's GLM_ROWS_PER_WG records)
+inline int64_t glm_wgroups(int64_t count) { return (count + GLM_ROWS_PER_WG - 1) / GLM_ROWS_PER_WG; }
+inline int64_t glm_gram_blocks(int64_t count) { return (count + GLM_GRAM_BLOCK - 1) / GLM_GRAM_BLOCK; }
+inline int glm_gram_grid(int64_t count)
+{
+    const int64_t b = glm_gram_blocks(count);
+    return (int)(b < GLM_GRAM_MAXGRID ? b : GLM_GRAM_MAXGRID);
+}
+
+// work-groups of the weight pass for this d that one CU holds at a time
+int glm_wpass_blocks_per_cu(int d);
+
+// W[m] = sum_i w(a_{m0+m} . theta_i) for m < count, over S ranges of the
+// particles' tiles (1 <= S <= glm_tiles(nrows)) added in ascending order;
+// wpart holds S * glm_wgroups(count) * GLM_ROWS_PER_WG doubles, W count
+hipError_t launch_glm_weights(int d, const double *X, int64_t nrows, const double *rec, int64_t m0,
+                              int64_t count, int S, double *wpart, double *W, hipStream_t stream);
+// H (d x d, exactly symmetric) = scale sum_m W_m a_m a_m^T + diag I over the
+// window, in blocks of GLM_GRAM_BLOCK records added in ascending order; W ==
+// nullptr: every W_m = wconst; hpart holds glm_gram_grid(count) * d (d + 1) / 2
+hipError_t launch_glm_wgram(int d, const double *rec, int64_t m0, int64_t count, const double *W,
+                            double wconst, double scale, double diag, double *hpart, double *H,
+                            hipStream_t stream);
+
 } // namespace svgd_amd

@@ -7,10 +7,14 @@ ARCH ?= gfx950
 HIPFLAGS ?= -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wall -Wno-unused-result
 SRC_DIR := svgdcpp_amd/csrc
 LIB := svgdcpp_amd/libsvgdcpp_amd.so
-OBJS := $(SRC_DIR)/svgd_kernels.o $(SRC_DIR)/svgd_collect.o $(SRC_DIR)/svgd_ksd.o $(SRC_DIR)/svgd_capi.o $(SRC_DIR)/plan.o $(SRC_DIR)/median_plan.o $(SRC_DIR)/host_models.o \
+# the runtime behind the C ABI: svgd_capi.cpp and one unit per phase (ctx.h)
+CTX_OBJS := $(SRC_DIR)/svgd_capi.o $(SRC_DIR)/ctx_comm.o $(SRC_DIR)/ctx_timing.o $(SRC_DIR)/ctx_median.o $(SRC_DIR)/ctx_phi.o \
+        $(SRC_DIR)/ctx_create.o $(SRC_DIR)/ctx_host_step.o $(SRC_DIR)/ctx_models.o $(SRC_DIR)/ctx_ksd.o
+OBJS := $(SRC_DIR)/svgd_kernels.o $(SRC_DIR)/svgd_collect.o $(SRC_DIR)/svgd_ksd.o $(CTX_OBJS) $(SRC_DIR)/plan.o $(SRC_DIR)/median_plan.o $(SRC_DIR)/host_models.o \
         $(SRC_DIR)/hostcomm.o $(SRC_DIR)/svgd_glm.o $(SRC_DIR)/svgd_gauss_hess.o $(SRC_DIR)/host_glm.o
 HDRS := $(SRC_DIR)/svgd_kernels.h $(SRC_DIR)/select_state.h $(SRC_DIR)/median_plan.h $(SRC_DIR)/built.h $(SRC_DIR)/dispatch.h $(SRC_DIR)/plan.h $(SRC_DIR)/svgd_ksd.h $(SRC_DIR)/svgd_device.h $(SRC_DIR)/svgd_exp_table.h \
-        $(SRC_DIR)/svgd_glm.h $(SRC_DIR)/svgd_gauss_hess.h $(SRC_DIR)/host_glm.h include/svgdcpp_amd/svgd_capi.h
+        $(SRC_DIR)/svgd_glm.h $(SRC_DIR)/svgd_gauss_hess.h $(SRC_DIR)/host_glm.h include/svgdcpp_amd/svgd_capi.h \
+        $(SRC_DIR)/ctx.h $(SRC_DIR)/resource.h $(SRC_DIR)/hostcomm.h $(SRC_DIR)/host_models.h
 
 all: $(LIB)
 
@@ -22,8 +26,12 @@ $(SRC_DIR)/%.o: $(SRC_DIR)/%.hip $(HDRS)
 $(SRC_DIR)/svgd_collect.o: $(SRC_DIR)/svgd_collect.hip $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -mllvm -amdgpu-mfma-vgpr-form -c $< -o $@
 
-$(SRC_DIR)/svgd_capi.o: $(SRC_DIR)/svgd_capi.cpp $(HDRS)
+$(CTX_OBJS): $(SRC_DIR)/%.o: $(SRC_DIR)/%.cpp $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
+
+# the link's object list, for the variant builds (tools/build_*_variant*.sh)
+print-objs:
+	@echo $(OBJS)
 
 # host-only translation units (no device code)
 $(SRC_DIR)/plan.o: $(SRC_DIR)/plan.cpp $(HDRS)
@@ -101,7 +109,8 @@ sanitize: build/sanitize_host
 
 # the host GLM (host_glm.cpp) under the same sanitizers, with a driver of its
 # own (tests/cpp/sanitize_glm.cpp).  Run by tests/test_sanitize_glm.py.
-build/sanitize_glm: tests/cpp/sanitize_glm.cpp $(SRC_DIR)/host_glm.cpp $(SRC_DIR)/host_glm.h include/svgdcpp_amd/svgd_capi.h
+build/sanitize_glm: tests/cpp/sanitize_glm.cpp $(SRC_DIR)/host_glm.cpp $(SRC_DIR)/host_glm.h include/svgdcpp_amd/svgd_capi.h \
+        $(SRC_DIR)/ctx.h $(SRC_DIR)/resource.h $(SRC_DIR)/hostcomm.h $(SRC_DIR)/host_models.h
 	@mkdir -p build
 	$(CXX) -O1 -g -std=c++17 -fopenmp $(SAN) tests/cpp/sanitize_glm.cpp $(SRC_DIR)/host_glm.cpp -o $@ -lm
 
@@ -112,4 +121,4 @@ clean:
 	rm -f $(OBJS) $(LIB) $(CPP_BINS) build/sanitize_host build/sanitize_glm
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle cpp clean sanitize sanitize_glm
+.PHONY: all oracle cpp clean sanitize sanitize_glm print-objs

@@ -4,7 +4,7 @@
 // the CPU oracle (oracle/svgd_oracle.c, test infrastructure) built with
 // -fsanitize=address,undefined and exercised with cross-checks
 // (`make sanitize`, run by tests/test_sanitize.py).  The HIP-side host code
-// (svgd_capi.cpp, hostcomm.cpp) drives the GPU and is covered by the -m gpu
+// (svgd_capi.cpp, ctx_*.cpp, hostcomm.cpp) drives the GPU and is covered by the -m gpu
 // tests instead: GPU sanitizers are not available on this pool.
 #include <cmath>
 #include <cstdint>

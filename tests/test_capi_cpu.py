@@ -26,6 +26,20 @@ def test_library_exports_every_declared_symbol():
     assert sorted(C.SIGNATURES) == declared
 
 
+def test_defined_symbols_equal_declared_functions():
+    """The library defines exactly the svgd_* functions the header declares:
+    each once, none lost between the runtime's translation units, no other
+    svgd_* text symbol exported."""
+    import subprocess
+
+    out = subprocess.run(["nm", "-D", "--defined-only", C.LIB_PATH], check=True, capture_output=True,
+                         text=True).stdout
+    defined = [f[2] for f in (line.split() for line in out.splitlines())
+               if len(f) == 3 and f[1] in "TtWw" and f[2].startswith("svgd_")]
+    assert len(defined) == len(set(defined)), sorted(defined)
+    assert sorted(defined) == _declared_functions()
+
+
 def test_binding_loads():
     assert C.lib() is not None
 

@@ -106,8 +106,9 @@ def test_plan_refuses_bad_arguments():
 
 def test_knob_reader_matches_documented_table():
     """Every SVGD_* variable the library reads is named once, in read_knobs
-    (svgd_capi.cpp), and INTEGRATION.md section 7 documents exactly that set."""
-    src = open(os.path.join(ROOT, "svgdcpp_amd", "csrc", "svgd_capi.cpp")).read()
+    (ctx_create.cpp), and INTEGRATION.md section 7 documents exactly that set."""
+    csrc = os.path.join(ROOT, "svgdcpp_amd", "csrc")
+    src = open(os.path.join(csrc, "ctx_create.cpp")).read()
     body = src[src.index("Knobs read_knobs()"):]
     body = body[:body.index("\n}\n")]
     read = re.findall(r'"(SVGD_[A-Z0-9_]+)"', body)
@@ -120,5 +121,8 @@ def test_knob_reader_matches_documented_table():
     assert set(rows) == set(read)
     # the environment is read nowhere else in the library
     assert src.count("getenv") == body.count("getenv")
-    for f in ("plan.cpp", "hostcomm.cpp", "host_models.cpp", "svgd_kernels.hip", "svgd_collect.hip", "svgd_ksd.hip"):
-        assert "getenv" not in open(os.path.join(ROOT, "svgdcpp_amd", "csrc", f)).read(), f
+    others = [f for f in sorted(os.listdir(csrc))
+              if f.endswith((".cpp", ".hip", ".h", ".inc")) and f != "ctx_create.cpp"]
+    assert len(others) >= 30, others
+    for f in others:
+        assert "getenv" not in open(os.path.join(csrc, f)).read(), f

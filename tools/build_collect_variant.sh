@@ -11,5 +11,7 @@ make -s
 mkdir -p tools/ablibs /tmp/colvar
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-result -mllvm -amdgpu-mfma-vgpr-form \
   "$@" -c $S/svgd_collect.hip -o /tmp/colvar/$name.o
-/opt/rocm/bin/hipcc -shared --offload-arch=gfx950 -o tools/ablibs/$name.so $S/svgd_kernels.o /tmp/colvar/$name.o \
-  $S/svgd_capi.o $S/plan.o $S/host_models.o $S/hostcomm.o -L/opt/rocm/lib -lrccl -fopenmp -Wl,-rpath,/opt/rocm/lib
+# every object of the library (the Makefile's list) but the one replaced here
+OTHER=$(make -s print-objs | tr ' ' '\n' | grep -v "^$S/svgd_collect\.o$" | tr '\n' ' ')
+/opt/rocm/bin/hipcc -shared --offload-arch=gfx950 -o tools/ablibs/$name.so /tmp/colvar/$name.o \
+  $OTHER -L/opt/rocm/lib -lrccl -fopenmp -Wl,-rpath,/opt/rocm/lib

@@ -8,7 +8,9 @@ cd "$(dirname "$0")/.."
 S=svgdcpp_amd/csrc
 T=/tmp/phivar
 mkdir -p $T tools/ablibs
-OTHER="$S/svgd_collect.o $S/svgd_capi.o $S/plan.o $S/host_models.o $S/hostcomm.o"
+# every object of the library (the Makefile's list) but the one replaced here
+make -s
+OTHER=$(make -s print-objs | tr ' ' '\n' | grep -v "^$S/svgd_kernels\.o$" | tr '\n' ' ')
 F="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-result -I$S"
 link() { /opt/rocm/bin/hipcc -shared --offload-arch=gfx950 -o tools/ablibs/$1.so $2 $OTHER -L/opt/rocm/lib -lrccl -fopenmp -Wl,-rpath,/opt/rocm/lib; }
 pids=()

@@ -132,6 +132,43 @@ public:
         CheckRc(svgd_glm_neg_hess_sum(const_cast<void *>(GlmHandle()), X, n, H));
     }
 
+    Link GetLink() const { return link_; }
+    double GetLikScale() const { return lik_scale_; }
+
+    /** Posterior predictive on the m held-out rows A (m x d, one test row per
+     *  matrix row; labels y optional) over the n particles X (n x d
+     *  row-major), on the host with the model's own link and lik_scale
+     *  (svgd_glm_predict_host).  Any output may be null; lpd needs y. */
+    void Predict(const double *X, int64_t n, const Eigen::MatrixXd &A, const Eigen::VectorXd *y,
+                 Eigen::VectorXd *mean, Eigen::VectorXd *var, Eigen::VectorXd *lpd) const
+    {
+        if ((size_t)A.cols() != (size_t)dimension_ || (y && y->rows() != A.rows()))
+            throw DimensionMismatchException("Test rows do not match the model dimension or the labels.");
+        const std::vector<double> a = RowMajor(A);
+        const int64_t m = (int64_t)A.rows();
+        for (Eigen::VectorXd *o : {mean, var, lpd})
+            if (o)
+                o->resize(A.rows());
+        const int rc = svgd_glm_predict_host((int)link_, lik_scale_, (int)dimension_, a.data(), y ? y->data() : nullptr,
+                                             m, X, n, mean ? mean->data() : nullptr, var ? var->data() : nullptr,
+                                             lpd ? lpd->data() : nullptr);
+        if (rc == SVGD_ERR_DIM)
+            throw DimensionMismatchException("Prediction needs at least one test row and one particle.");
+        if (rc != SVGD_OK)
+            svgdcpp::ThrowFromCode(rc, SVGDCPP_LOG_PREFIX + "[Argument Error] Prediction: the test data must be "
+                                                            "finite and logistic labels in [0, 1].");
+    }
+
+    /** A (rows x cols) as row-major doubles. */
+    static std::vector<double> RowMajor(const Eigen::MatrixXd &A)
+    {
+        std::vector<double> a((size_t)A.rows() * A.cols());
+        for (long r = 0; r < A.rows(); ++r)
+            for (long c = 0; c < A.cols(); ++c)
+                a[(size_t)r * A.cols() + c] = A(r, c);
+        return a;
+    }
+
 protected:
     static void CheckRc(int rc)
     {

@@ -308,6 +308,50 @@ public:
         return unbiased ? u : v;
     }
 
+    /** What Predict returns: per test row the predictive mean, its variance
+     *  over the particles and (with labels, else empty) the log predictive
+     *  density. */
+    struct Prediction
+    {
+        Eigen::VectorXd mean, var, lpd;
+    };
+
+    /** Extension: the posterior predictive of the GeneralizedLinearModel on
+     *  the held-out rows A (m x d; labels y optional) over the caller's
+     *  coordinate matrix, on the device (svgd_glm_predict).  The context is
+     *  handled as in ComputeKSD; in a sharded run every rank calls it. */
+    Prediction Predict(const Eigen::MatrixXd &A, const Eigen::VectorXd *y = nullptr)
+    {
+        const GeneralizedLinearModel *glm = dynamic_cast<const GeneralizedLinearModel *>(model_ptr_.get());
+        if (!glm)
+            throw std::invalid_argument(SVGDCPP_LOG_PREFIX + "[Argument Error] SVGD::Predict needs a GeneralizedLinearModel.");
+        if (A.cols() != (long)dimension_ || (y && y->rows() != A.rows()))
+            throw DimensionMismatchException("Test rows do not match the model dimension or the labels.");
+        std::shared_ptr<svgd_ctx> tmp;
+        svgd_ctx *c = ctx_.get();
+        if (!c)
+        {
+            const int rc = svgd_create(&c, dimension_, (int64_t)num_particles_, SVGD_F64, device_);
+            tmp.reset(c, [](svgd_ctx *p) { svgd_destroy(p); });
+            if (rc != SVGD_OK)
+                svgdcpp::ThrowFromCode(rc, svgd_last_error(c));
+        }
+        auto check = [&](int rc) {
+            if (rc != SVGD_OK)
+                svgdcpp::ThrowFromCode(rc, svgd_last_error(c));
+        };
+        check(svgd_set_particles(c, coord_matrix_ptr_->data()));
+        const std::vector<double> a = GeneralizedLinearModel::RowMajor(A);
+        Prediction out;
+        out.mean.resize(A.rows());
+        out.var.resize(A.rows());
+        if (y)
+            out.lpd.resize(A.rows());
+        check(svgd_glm_predict(c, (int)glm->GetLink(), glm->GetLikScale(), a.data(), y ? y->data() : nullptr,
+                               (int64_t)A.rows(), out.mean.data(), out.var.data(), y ? out.lpd.data() : nullptr));
+        return out;
+    }
+
     /** The context (for callers that need the C ABI directly); null on the
      *  generic-kernel host path. */
     svgd_ctx *Context() const { return ctx_.get(); }

@@ -362,6 +362,33 @@ int svgd_device_neg_hess_sum(svgd_ctx *ctx, double *H_shard_out);
  * svgd_set_device_glm leave the switch alone. */
 int svgd_set_device_hessian(svgd_ctx *ctx, int on);
 
+/* Posterior prediction of a GLM on held-out rows a_j (A: m x dim, row-major)
+ * and optional labels y_j, over all N particles theta_i (z_ij = a_j . theta_i,
+ * mu = sigma for SVGD_GLM_LOGISTIC and the identity for SVGD_GLM_GAUSSIAN):
+ *   mean_j = (1/N) sum_i mu(z_ij)
+ *   var_j  = (1/N) sum_i (mu(z_ij) - mean_j)^2     (>= 0: the spread over the particles)
+ *   lpd_j  = log (1/N) sum_i p(y_j | z_ij)          (only with y)
+ *     logistic  p = exp(y z - log(1 + e^z))         (y in [0, 1]; lik_scale is not used)
+ *     Gaussian  p = sqrt(s / 2 pi) exp(-s (y - z)^2 / 2),  s = lik_scale
+ * The sums are centred on mu(a_j . theta_bar), theta_bar the particles' mean,
+ * so var does not cancel.  The likelihood sum is not shifted: a record whose
+ * likelihood underflows at every particle gives lpd = -inf.  y may be NULL
+ * and any output may be NULL; lpd_out without y is SVGD_ERR_ARG.  Refused:
+ * NULL A, an unknown link, non-finite data, logistic labels outside [0, 1],
+ * lik_scale <= 0 (SVGD_ERR_ARG); m < 1, dim < 1 or nrows < 1 (SVGD_ERR_DIM).
+ *
+ * host, no GPU: particles X (nrows x dim), OpenMP over records, each record's
+ * sums in particle order (independent of the thread count) */
+int svgd_glm_predict_host(int link, double lik_scale, int dim, const double *A, const double *y,
+                          int64_t m, const double *X, int64_t nrows,
+                          double *mean_out, double *var_out, double *lpd_out);
+/* device: the context's current particles; collective in multi-GPU mode, every
+ * rank passes the same test data and gets the same m-vectors.  Needs no
+ * device model; fp64 whatever the context's dtype; two calls on the same
+ * state return the same bits.  A pure observer like svgd_ksd.  d <= 64. */
+int svgd_glm_predict(svgd_ctx *ctx, int link, double lik_scale, const double *A, const double *y,
+                     int64_t m, double *mean_out, double *var_out, double *lpd_out);
+
 /* Kernelized Stein discrepancy of the current particles with the isotropic
  * RBF kernel k = exp(-a |x - y|^2), whatever scale method the context steps
  * with.  For s_i = grad log p(x_i), r = x_i - x_j:

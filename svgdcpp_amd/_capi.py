@@ -134,6 +134,9 @@ SIGNATURES = {
     "svgd_set_device_glm_batch": (ctypes.c_int, [_P, _I64, _I64]),
     "svgd_device_neg_hess_sum": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double)]),
     "svgd_set_device_hessian": (ctypes.c_int, [_P, ctypes.c_int]),
+    "svgd_glm_predict_host": (ctypes.c_int, [ctypes.c_int, ctypes.c_double, ctypes.c_int, _D, _D, _I64, _D, _I64,
+                                             _D, _D, _D]),
+    "svgd_glm_predict": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_double, _D, _D, _I64, _D, _D, _D]),
 }
 
 _lib = None

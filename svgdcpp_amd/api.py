@@ -411,6 +411,7 @@ class GeneralizedLinearModel(Model):
             raise ValueError(PREFIX + "[Argument Error] GLM link must be 'logistic' or 'gaussian'.")
         super().__init__(A.shape[1])
         self.link_ = link
+        self.lik_scale_ = float(lik_scale)
         self.num_rows_ = A.shape[0]
         self.batch_ = (0, self.num_rows_)
         self._handle = None
@@ -468,6 +469,24 @@ class GeneralizedLinearModel(Model):
         C.lib().svgd_glm_neg_hess_sum(self._handle, C.dptr(X), X.shape[0], C.dptr(H))
         return H
 
+    def predict(self, X_rows, A, y=None):
+        """Posterior predictive on held-out rows A (m, d), labels y (m) optional,
+        over the particles X_rows (N, d), on the host (svgd_glm_predict_host)
+        with the model's own link and lik_scale: (mean, var), or
+        (mean, var, lpd) with y."""
+        X = self._rows(X_rows)
+        A, y = _predict_data(A, y, self.dimension_)
+        out = [np.empty(A.shape[0]) for _ in range(3 if y is not None else 2)]
+        rc = C.lib().svgd_glm_predict_host(self.LINKS[self.link_], self.lik_scale_, self.dimension_, C.dptr(A),
+                                           C.dptr(y), A.shape[0], C.dptr(X), X.shape[0], C.dptr(out[0]),
+                                           C.dptr(out[1]), C.dptr(out[2]) if y is not None else None)
+        if rc == C.SVGD_ERR_DIM:
+            raise DimensionMismatchException("Prediction needs at least one test row and one particle.")
+        if rc != C.SVGD_OK:
+            raise ValueError(PREFIX + "[Argument Error] Prediction: the test data must be finite and logistic "
+                             "labels in [0, 1].")
+        return tuple(out)
+
     def EvaluateLogModel(self, x):
         return float(self.log_model(np.asarray(x, dtype=np.float64).reshape(1, -1))[0])
 
@@ -479,6 +498,39 @@ class GeneralizedLinearModel(Model):
 
     def EvaluateLogModelHessian(self, x):
         return -self.neg_hess_sum(np.asarray(x, dtype=np.float64).reshape(1, -1))
+
+
+def _predict_data(A, y, dim):
+    """Test rows (m, dim) and optional labels (m) as contiguous float64."""
+    A = np.ascontiguousarray(A, dtype=np.float64)
+    if A.ndim != 2 or A.shape[1] != dim:
+        raise DimensionMismatchException("Test rows do not match the model dimension.")
+    if y is not None:
+        y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+        if y.shape[0] != A.shape[0]:
+            raise DimensionMismatchException("Test labels do not match the test rows.")
+    return A, y
+
+
+class PredictResult:
+    """What SVGD.Predict returns: per test row the predictive mean, its
+    variance over the particles (var) and, with labels, the log predictive
+    density (lpd, else None); total_var adds the observation's own variance
+    (1 / lik_scale, Gaussian link) or is the Bernoulli mean (1 - mean)
+    (logistic); mean_lpd, accuracy (logistic: the share with (mean >= 1/2) ==
+    (y >= 1/2)) and rmse (Gaussian link) need labels and are None otherwise
+    or for the other link."""
+
+    def __init__(self, link, lik_scale, mean, var, lpd=None, y=None):
+        self.mean, self.var, self.lpd = mean, var, lpd
+        logistic = link == "logistic"
+        self.total_var = mean * (1.0 - mean) if logistic else var + 1.0 / lik_scale
+        self.mean_lpd = float(np.mean(lpd)) if lpd is not None else None
+        self.accuracy = self.rmse = None
+        if y is not None and logistic:
+            self.accuracy = float(np.mean((mean >= 0.5) == (y >= 0.5)))
+        elif y is not None:
+            self.rmse = float(np.sqrt(np.mean((mean - y) ** 2)))
 
 
 def _builtin_glm(model):
@@ -974,6 +1026,20 @@ class Context:
                                      C.dptr(out)))
         return (v.value, u.value, out) if rows else (v.value, u.value)
 
+    def glm_predict(self, A, y=None, link="logistic", lik_scale=1.0):
+        """Posterior predictive of a GLM on held-out rows A (m, d), labels y
+        (m) optional, over the current particles of all ranks, on the device
+        (svgd_glm_predict; collective): (mean, var), or (mean, var, lpd) with
+        y.  No device model is needed."""
+        if link not in GeneralizedLinearModel.LINKS:
+            raise ValueError(PREFIX + "[Argument Error] GLM link must be 'logistic' or 'gaussian'.")
+        A, y = _predict_data(A, y, self.dim)
+        out = [np.empty(A.shape[0]) for _ in range(3 if y is not None else 2)]
+        self.check(self.lib.svgd_glm_predict(self.h, GeneralizedLinearModel.LINKS[link], float(lik_scale),
+                                             C.dptr(A), C.dptr(y), A.shape[0], C.dptr(out[0]), C.dptr(out[1]),
+                                             C.dptr(out[2]) if y is not None else None))
+        return tuple(out)
+
     def sync(self):
         self.check(self.lib.svgd_sync(self.h))
 
@@ -1167,6 +1233,26 @@ class SVGD:
             if c is not self.ctx:
                 c.close()
         return u if unbiased else v
+
+    def Predict(self, A, y=None):
+        """Posterior predictive of the GeneralizedLinearModel on held-out rows
+        A (m, d), labels y (m) optional, over the caller's coordinate matrix
+        (extension; svgd_glm_predict on the device): a PredictResult.  The
+        generic host-kernel path opens a context on the configured device for
+        the call; in a sharded run every rank calls it."""
+        if not isinstance(self.model_, GeneralizedLinearModel):
+            raise TypeError("SVGD.Predict needs a GeneralizedLinearModel")
+        m = self.model_
+        P = np.ascontiguousarray(np.asarray(self.coord_matrix_, dtype=np.float64).T)
+        c = self.ctx if self.ctx is not None else Context(P.shape[1], P.shape[0], device=self.device_)
+        try:
+            c.set_particles(P)
+            out = c.glm_predict(A, y, m.link_, m.lik_scale_)
+        finally:
+            if c is not self.ctx:
+                c.close()
+        yv = None if y is None else np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+        return PredictResult(m.link_, m.lik_scale_, out[0], out[1], out[2] if y is not None else None, yv)
 
     # -- generic kernel: the reference's ComputePhi on the host (SVGD.hpp:373-454)
     def _host_step(self, it):

@@ -3,7 +3,7 @@
 // One context = one GPU (one process per GPU in multi-GPU runs).  The context
 // owns every resource it allocates (resource.h): deleting it frees them all.
 // State that one unit alone reads or writes sits in that unit's group (co,
-// sym, ms, hs, tm, dm, ksd); what several units share stays flat.  The units
+// sym, ms, hs, tm, dm, ksd, pred); what several units share stays flat.  The units
 // (ctx_*.cpp, svgd_capi.cpp) call each other through the functions declared
 // at the end, per unit.
 #pragma once
@@ -381,6 +381,19 @@ struct svgd_ctx {
         svgd_amd::DevBuf<double> nrm, cvec, diag;
         svgd_amd::DevBuf<double> part, rows, bpart, out;
     } ksd;
+
+    // svgd_glm_predict's own work arrays (allocated by its first call, grown
+    // when a call brings more records): it reads X and nothing else of the
+    // step's state
+    struct Predict {
+        int cus = 0;                      // the device's CUs (0: not asked yet)
+        int64_t rec_cap = 0, m_cap = 0, part_cap = 0;
+        svgd_amd::DevBuf<double> mu, mpart; // the particles' mean, its column-sum partials
+        svgd_amd::DevBuf<double> rec;       // glm_padded(m) test records of glm_rec_stride(d) doubles
+        svgd_amd::DevBuf<double> cvec;      // m centres
+        svgd_amd::DevBuf<double> sums;      // 3 x m: A, B, L (all-reduced)
+        svgd_amd::DevBuf<double> part;      // S x 3 x ldw per-split sums
+    } pred;
 };
 
 namespace svgd_amd {

@@ -33,6 +33,24 @@ double glm_sigmoid(double z)
     const double e = std::exp(-std::fabs(z));
     return z >= 0.0 ? 1.0 / (1.0 + e) : e / (1.0 + e);
 }
+
+int glm_predict_check(int link, double lik_scale, int dim, const double *A, const double *y, int64_t m,
+                      const double *lpd_out)
+{
+    if (!A) return SVGD_ERR_ARG;
+    if (link != SVGD_GLM_LOGISTIC && link != SVGD_GLM_GAUSSIAN) return SVGD_ERR_ARG;
+    if (!(lik_scale > 0.0) || !std::isfinite(lik_scale)) return SVGD_ERR_ARG;
+    if (lpd_out && !y) return SVGD_ERR_ARG;
+    if (dim < 1 || m < 1) return SVGD_ERR_DIM;
+    for (int64_t e = 0; e < m * dim; ++e)
+        if (!std::isfinite(A[e])) return SVGD_ERR_ARG;
+    if (y)
+        for (int64_t e = 0; e < m; ++e) {
+            if (!std::isfinite(y[e])) return SVGD_ERR_ARG;
+            if (link == SVGD_GLM_LOGISTIC && !(y[e] >= 0.0 && y[e] <= 1.0)) return SVGD_ERR_ARG;
+        }
+    return SVGD_OK;
+}
 } // namespace svgd_amd
 
 namespace {
@@ -65,9 +83,77 @@ template <int LINK> void grad_rows(const HostGlm *g, const double *X, int64_t nr
     }
 }
 
+// The centred sums of svgd_glm_predict_host for every record: OpenMP over the
+// records, each record's sums in particle order.
+template <int LINK>
+void predict_rows(double lik_scale, int d, const double *A, const double *y, int64_t m, const double *X,
+                  int64_t nrows, const double *xbar, double *mean_out, double *var_out, double *lpd_out)
+{
+    const double N = (double)nrows, half_s = 0.5 * lik_scale;
+    const double lconst = svgd_amd::glm_predict_lconst(LINK, lik_scale);
+#pragma omp parallel for schedule(static)
+    for (int64_t j = 0; j < m; ++j) {
+        const double *a = A + j * d;
+        const double zbar = dotd(a, xbar, d);
+        const double c = LINK == SVGD_GLM_LOGISTIC ? svgd_amd::glm_sigmoid(zbar) : zbar;
+        const double yj = y ? y[j] : 0.0;
+        double sa = 0.0, sb = 0.0, sl = 0.0;
+        for (int64_t i = 0; i < nrows; ++i) {
+            const double z = dotd(a, X + i * d, d);
+            double dv, pv = 0.0;
+            if (LINK == SVGD_GLM_LOGISTIC) {
+                // sigma and exp(l) from e = exp(-|z|): no cancelling 1 - sigma
+                const double az = std::fabs(z), e = std::exp(-az), q = 1.0 + e;
+                dv = (z >= 0.0 ? 1.0 : e) / q - c;
+                if (y) {
+                    const double t = z >= 0.0 ? 1.0 - yj : yj;
+                    pv = (t == 0.0 ? 1.0 : t == 1.0 ? e : std::exp(-(az * t))) / q;
+                }
+            } else {
+                dv = z - c;
+                if (y) {
+                    const double r = yj - z;
+                    pv = std::exp(-((half_s * r) * r));
+                }
+            }
+            sa += dv;
+            sb += dv * dv;
+            sl += pv;
+        }
+        svgd_amd::glm_predict_finalize(c, sa, sb, sl, N, lconst, mean_out ? mean_out + j : nullptr,
+                                       var_out ? var_out + j : nullptr, lpd_out ? lpd_out + j : nullptr);
+    }
+}
+
 } // namespace
 
 extern "C" {
+
+int svgd_glm_predict_host(int link, double lik_scale, int dim, const double *A, const double *y, int64_t m,
+                          const double *X, int64_t nrows, double *mean_out, double *var_out, double *lpd_out)
+{
+    // mean_m = (1/N) sum_i mu(z_im), var_m its spread over the particles and
+    // lpd_m = log (1/N) sum_i p(y_m | z_im), from sums centred on
+    // c_m = mu(a_m . theta_bar) so that the variance does not cancel
+    const int rc = svgd_amd::glm_predict_check(link, lik_scale, dim, A, y, m, lpd_out);
+    if (rc != SVGD_OK) return rc;
+    if (!X) return SVGD_ERR_ARG;
+    if (nrows < 1) return SVGD_ERR_DIM;
+    std::vector<double> xbar;
+    try {
+        xbar.assign((size_t)dim, 0.0);
+    } catch (const std::bad_alloc &) {
+        return SVGD_ERR_RUNTIME;
+    }
+    for (int64_t i = 0; i < nrows; ++i)
+        for (int k = 0; k < dim; ++k) xbar[(size_t)k] += X[i * dim + k];
+    for (int k = 0; k < dim; ++k) xbar[(size_t)k] /= (double)nrows;
+    if (link == SVGD_GLM_LOGISTIC)
+        predict_rows<SVGD_GLM_LOGISTIC>(lik_scale, dim, A, y, m, X, nrows, xbar.data(), mean_out, var_out, lpd_out);
+    else
+        predict_rows<SVGD_GLM_GAUSSIAN>(lik_scale, dim, A, y, m, X, nrows, xbar.data(), mean_out, var_out, lpd_out);
+    return SVGD_OK;
+}
 
 int svgd_glm_create(void **out, int dim, int64_t m, const double *A, const double *y, int link,
                     double lik_scale, double prior_prec)

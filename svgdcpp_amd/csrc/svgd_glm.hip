@@ -31,15 +31,7 @@
 namespace svgd_amd {
 namespace glm {
 
-#include "svgd_exp_table.h" // EXP2_TAB4096 (this translation unit's copy)
-
-typedef double d4 __attribute__((ext_vector_type(4)));
-
-constexpr double LOG2E = 0x1.71547652b82fep+0;
-constexpr int EXP_TB = 4096; // exp table entries
-constexpr int NT = 64 * GLM_WAVES;
-// exponents below 2^-1100 give exactly 0 (the smallest subnormal is 2^-1074)
-constexpr double U_MIN = -1100.0 * EXP_TB;
+#include "svgd_glm_dev.h" // the table exponential's pieces, d4, NT, blocks_per_cu
 
 template <int KP, int LINK> struct Geom {
     static constexpr int RS = glm_rec_stride(KP);
@@ -50,13 +42,6 @@ template <int KP, int LINK> struct Geom {
     static constexpr int TAB = LINK == SVGD_GLM_LOGISTIC ? EXP_TB : 0;
     static constexpr int LDS = (2 * TW + TAB) * 8;  // two tile buffers + the table
 };
-
-// 2^(f/4096), |f| <= 1/2: 1 + c1 f + c2 f^2 with the coefficients levelled
-// over the interval (relative error <= 2.6e-14, tools/make_exp_table.py)
-__device__ __forceinline__ double exp2_4096_poly(double f)
-{
-    return fma(fma(0x1.ebfbdff82c58fp-27, f, 0x1.62e42ff4f7b0ap-13), f, 1.0);
-}
 
 // sigma(z) from e = exp(-|z|) in both tails: 1 / (1 + e) or e / (1 + e); an
 // underflowing e is exactly 0
@@ -424,19 +409,6 @@ WPassFn wpass_fn(int kp)
     if (kp % 4 == 0)
         dispatch_range<1, 16>(kp / 4, [&](auto q) { f = &k_glm_wpass<4 * decltype(q)::value>; });
     return f;
-}
-
-// work-groups of 8 waves that one CU holds at a time: two waves per SIMD each
-// (512 VGPRs per lane, allocated in eights), capped by the 160 KiB of LDS
-int blocks_per_cu(const void *f)
-{
-    hipFuncAttributes fa;
-    if (!f || hipFuncGetAttributes(&fa, f) != hipSuccess) return 1;
-    const int regs = (fa.numRegs > 0 ? fa.numRegs + 7 : 8) / 8 * 8;
-    const int by_regs = 512 / regs / 2 < 4 ? 512 / regs / 2 : 4;
-    const int by_lds = fa.sharedSizeBytes > 0 ? (int)(163840 / fa.sharedSizeBytes) : 4;
-    const int b = by_regs < by_lds ? by_regs : by_lds;
-    return b > 1 ? b : 1;
 }
 
 } // namespace glm

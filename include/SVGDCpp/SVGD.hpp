@@ -27,8 +27,8 @@
  * every rank passes the full coordinate matrix, owns rows [row0, row1) of
  * the step and ends Run() with all of them (svgd_create_dist).
  * Requirements of the device path: the kernel is a GaussianRBFKernel
- * (Median, Hessian or Constant scale) and the optimizer is Adam, AdaGrad or
- * RMSProp.  With the Hessian scale, the kernel's model sums -hess log p(X_t)
+ * (Median, Hessian or Constant scale) or an InverseMultiquadricKernel (Median
+ * or Constant scale) and the optimizer is Adam, AdaGrad or RMSProp.  With the Hessian scale, the kernel's model sums -hess log p(X_t)
  * on the host between the two device calls (GaussianRBFKernel.hpp:189-210).
  * LogIntermediateMatrices re-evaluates K and Kg on the host from the step's
  * scale (debug aid for small N, same text format as SVGD.hpp:345-365).
@@ -40,7 +40,8 @@
  * UpdateLocation(x_i), then k(x_j, x_i) and grad k(x_j, x_i) for every j),
  * with the plugin optimizer's own Step and the clamp.  The choice is made
  * once, by kernel type, at construction (UsesDevicePath()); a
- * GaussianRBFKernel never takes the host path, and the host path needs no GPU.
+ * GaussianRBFKernel or InverseMultiquadricKernel never takes the host path,
+ * and the host path needs no GPU.
  */
 #ifndef SVGDCPP_AMD_SVGD_HPP
 #define SVGDCPP_AMD_SVGD_HPP
@@ -52,6 +53,7 @@
 
 #include "Core.hpp"
 #include "Kernel/GaussianRBFKernel.hpp"
+#include "Kernel/InverseMultiquadricKernel.hpp"
 #include "Kernel/Kernel.hpp"
 #include "Model/Model.hpp"
 #include "Model/MultivariateNormal.hpp"
@@ -161,7 +163,8 @@ public:
         if (optimizer_ptr_ == nullptr)
             throw std::invalid_argument(SVGDCPP_LOG_PREFIX + "[Argument Error] Invalid Optimizer object pointer.");
         rbf_ptr_ = std::dynamic_pointer_cast<GaussianRBFKernel>(kernel_ptr_);
-        if (!rbf_ptr_)
+        imq_ptr_ = std::dynamic_pointer_cast<InverseMultiquadricKernel>(kernel_ptr_);
+        if (!rbf_ptr_ && !imq_ptr_)
         {
             // generic kernel: the reference's per-pair ComputePhi on the host,
             // the whole problem in this process -- the sharding options
@@ -253,7 +256,12 @@ public:
                 LogStep(iter, hx, hg);
         }
         Check(svgd_get_particles(c, coord_matrix_ptr_->data()));
-        if (rbf_ptr_->GetScaleMethod() != GaussianRBFKernel::ScaleMethod::Constant && num_iterations_ > 0)
+        if (imq_ptr_)
+        {
+            if (imq_ptr_->GetScaleMethod() != InverseMultiquadricKernel::ScaleMethod::Constant && num_iterations_ > 0)
+                imq_ptr_->UpdateParameters({Eigen::MatrixXd::Constant(1, 1, LastScaleMatrix()(0, 0))});
+        }
+        else if (rbf_ptr_->GetScaleMethod() != GaussianRBFKernel::ScaleMethod::Constant && num_iterations_ > 0)
             rbf_ptr_->UpdateParameters({LastScaleMatrix()});
         if (log_intermediate_matrices_)
             WriteIntermediateMatricesToFile();
@@ -356,9 +364,9 @@ public:
      *  generic-kernel host path. */
     svgd_ctx *Context() const { return ctx_.get(); }
 
-    /** True for a GaussianRBFKernel (the HIP path), false for the generic
-     *  host path of any other kernel. */
-    bool UsesDevicePath() const { return rbf_ptr_ != nullptr; }
+    /** True for a GaussianRBFKernel or an InverseMultiquadricKernel (the HIP
+     *  path), false for the generic host path of any other kernel. */
+    bool UsesDevicePath() const { return rbf_ptr_ != nullptr || imq_ptr_ != nullptr; }
 
     /** True when Step() takes the one-call pipelined step (svgd_step_host_model):
      *  a built-in Gaussian model of exactly the Model / MultivariateNormal
@@ -371,7 +379,7 @@ public:
         const Model &m = *model_ptr_;
         if (typeid(m) != typeid(Model) && typeid(m) != typeid(MultivariateNormal))
             return false;
-        return rbf_ptr_->GetScaleMethod() != GaussianRBFKernel::ScaleMethod::Hessian;
+        return !HessianScale();
     }
 
     /** True when Step() runs wholly on the device, grad log p included
@@ -388,8 +396,7 @@ public:
         const Model &m = *model_ptr_;
         if (typeid(m) != typeid(GeneralizedLinearModel))
             return false;
-        return rbf_ptr_->GetScaleMethod() != GaussianRBFKernel::ScaleMethod::Hessian ||
-               rbf_ptr_->GetTargetModel() == model_ptr_;
+        return !HessianScale() || rbf_ptr_->GetTargetModel() == model_ptr_;
     }
 
     /** Rows [row0, row1) of the particles this rank steps (all of them on one GPU). */
@@ -424,7 +431,7 @@ protected:
         }
         const int64_t rows = row1_ - row0_;
         Check(svgd_begin_step(c, hx));
-        if (rbf_ptr_->GetScaleMethod() == GaussianRBFKernel::ScaleMethod::Hessian)
+        if (HessianScale())
         {
             std::vector<double> H((size_t)dimension_ * dimension_);
             rbf_ptr_->GetTargetModel()->NegHessSumBatch(hx, rows, H.data());
@@ -569,11 +576,27 @@ protected:
         }
         // a Hessian scale on the device step: the device model supplies the sum
         Check(svgd_set_device_hessian(
-            c, UsesDeviceModelStep() && rbf_ptr_->GetScaleMethod() == GaussianRBFKernel::ScaleMethod::Hessian));
+            c, UsesDeviceModelStep() && HessianScale()));
+    }
+
+    /** The RBF kernel's Hessian scale (the IMQ kernel has scalar scales only). */
+    bool HessianScale() const
+    {
+        return rbf_ptr_ && rbf_ptr_->GetScaleMethod() == GaussianRBFKernel::ScaleMethod::Hessian;
     }
 
     void ConfigureScale()
     {
+        if (imq_ptr_)
+        {
+            // (a scalar scale first: the IMQ kernel refuses a context on a matrix scale)
+            if (imq_ptr_->GetScaleMethod() == InverseMultiquadricKernel::ScaleMethod::Constant)
+                Check(svgd_set_scale(ctx_.get(), SVGD_SCALE_FIXED, imq_ptr_->GetScale()));
+            else
+                Check(svgd_set_scale(ctx_.get(), SVGD_SCALE_MEDIAN, 0.0));
+            Check(svgd_set_kernel(ctx_.get(), SVGD_KERNEL_IMQ));
+            return;
+        }
         switch (rbf_ptr_->GetScaleMethod())
         {
         case GaussianRBFKernel::ScaleMethod::Constant:
@@ -622,6 +645,18 @@ protected:
             {
                 for (long k = 0; k < d; ++k)
                     diff[(size_t)k] = hx[j * d + k] - hx[i * d + k];
+                if (imq_ptr_)
+                { // the class's closed form at the step's scale a (M = a I)
+                    const double a = M(0, 0);
+                    double r2 = 0.0;
+                    for (long k = 0; k < d; ++k)
+                        r2 += diff[(size_t)k] * diff[(size_t)k];
+                    const double kv = 1.0 / std::sqrt(1.0 + a * r2);
+                    K(j, i) = kv;
+                    for (long k = 0; k < d; ++k)
+                        Kg(j * d + k, i) = -a * diff[(size_t)k] * (kv * kv * kv);
+                    continue;
+                }
                 double u = 0.0;
                 for (long r = 0; r < d; ++r)
                 {
@@ -672,6 +707,7 @@ protected:
     std::vector<double> lower_, upper_;
     std::shared_ptr<Kernel> kernel_ptr_;
     std::shared_ptr<GaussianRBFKernel> rbf_ptr_;
+    std::shared_ptr<InverseMultiquadricKernel> imq_ptr_; // at most one of the two is set
     std::shared_ptr<Model> model_ptr_;
     std::shared_ptr<Optimizer> optimizer_ptr_;
     std::shared_ptr<Eigen::MatrixXd> coord_matrix_ptr_;

@@ -406,6 +406,36 @@ int svgd_glm_predict(svgd_ctx *ctx, int link, double lik_scale, const double *A,
 int svgd_ksd(svgd_ctx *ctx, const double *G_shard, double a, double *ksd2_v, double *ksd2_u,
              double *rows_shard_out);
 
+/* ---- inverse multiquadric kernel (extension) ------------------------------
+ *   k(x, x')  = (1 + a |x - x'|^2)^(-1/2)              a >= 0 (a = 0: k = 1)
+ *   grad_x' k = -a (x' - x) k^3
+ *   phi_i     = (1/N) sum_j [ k_ij G_j + a k_ij^3 (x_i - x_j) ]   (SVGD.hpp:407-454 with this kernel)
+ * The exponent -1/2 and the offset 1 are fixed.  a comes from the scale
+ * methods above: SVGD_SCALE_MEDIAN (a = ln N / med^2, the same median) or
+ * SVGD_SCALE_FIXED.  SVGD_SCALE_HESSIAN and SVGD_SCALE_MATRIX with the IMQ
+ * kernel are refused with SVGD_ERR_ARG, whichever of the two calls comes
+ * second.
+ *
+ * svgd_set_kernel chooses the kernel of svgd_phi and of every step call of
+ * this context (every rank alike); the default is SVGD_KERNEL_RBF.  With
+ * SVGD_KERNEL_IMQ, phi_hat is computed in fp64 whatever the context's dtype
+ * (the median stays the dtype's), the optimizer update is a launch of its
+ * own, and two calls on the same state return the same bits.
+ * svgd_phi_kernel_name reports the IMQ pass while it is set.  svgd_ksd stays
+ * the RBF statistic whatever kernel is set.  d <= 64. */
+#define SVGD_KERNEL_RBF 0
+#define SVGD_KERNEL_IMQ 1
+int svgd_set_kernel(svgd_ctx *ctx, int kind);
+int svgd_get_kernel(const svgd_ctx *ctx, int *kind);
+/* host, no GPU: phi_out (nrows x dim) = phi_i of the definition above for the
+ * rows [row0, row0 + nrows) of X (n x dim) with G (n x dim), by direct
+ * differences; OpenMP over rows, each row's sums in particle order
+ * (independent of the thread count).  Refused: NULL pointers, a < 0 or not
+ * finite, a row window outside [0, n] (SVGD_ERR_ARG); dim < 1 or n < 1
+ * (SVGD_ERR_DIM). */
+int svgd_imq_phi_host(int dim, int64_t n, const double *X, const double *G, double a, int64_t row0,
+                      int64_t nrows, double *phi_out);
+
 /* ---- host-only planning helpers (no GPU needed) ------------------------ */
 
 /* Row shard of rank r among `world` for n particles: equal chunks of

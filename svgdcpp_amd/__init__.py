@@ -7,13 +7,13 @@ Importing the API does not touch the GPU; creating an SVGD/Context does.
 """
 from . import _capi
 from .api import (SVGD, AdaGrad, Adam, Context, DeviceError, DimensionMismatchException,
-                  GaussianRBFKernel, GaussianSum, GeneralizedLinearModel, Kernel, Model,
+                  GaussianRBFKernel, GaussianSum, GeneralizedLinearModel, InverseMultiquadricKernel, Kernel, Model,
                   MultivariateNormal, Optimizer, PredictResult, RMSProp, SVGDOptions, UnsetException, plan_phi_name)
 
 __all__ = [
     "SVGD", "SVGDOptions", "Context", "Model", "MultivariateNormal", "GaussianSum",
     "GeneralizedLinearModel", "PredictResult", "Kernel",
-    "GaussianRBFKernel", "Optimizer", "Adam", "AdaGrad", "RMSProp", "DimensionMismatchException",
+    "GaussianRBFKernel", "InverseMultiquadricKernel", "Optimizer", "Adam", "AdaGrad", "RMSProp", "DimensionMismatchException",
     "UnsetException", "DeviceError", "lib", "plan_phi_name",
 ]
 

@@ -30,6 +30,8 @@ SVGD_SCALE_MEDIAN = 0
 SVGD_SCALE_FIXED = 2
 SVGD_SCALE_MATRIX = 3
 SVGD_SCALE_HESSIAN = 1
+SVGD_KERNEL_RBF = 0
+SVGD_KERNEL_IMQ = 1
 SVGD_GLM_LOGISTIC = 0
 SVGD_GLM_GAUSSIAN = 1
 SVGD_MEDIAN_DIRECT = 0
@@ -136,6 +138,9 @@ SIGNATURES = {
     "svgd_set_device_hessian": (ctypes.c_int, [_P, ctypes.c_int]),
     "svgd_glm_predict_host": (ctypes.c_int, [ctypes.c_int, ctypes.c_double, ctypes.c_int, _D, _D, _I64, _D, _I64,
                                              _D, _D, _D]),
+    "svgd_set_kernel": (ctypes.c_int, [_P, ctypes.c_int]),
+    "svgd_get_kernel": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int)]),
+    "svgd_imq_phi_host": (ctypes.c_int, [ctypes.c_int, _I64, _D, _D, ctypes.c_double, _I64, _I64, _D]),
     "svgd_glm_predict": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_double, _D, _D, _I64, _D, _D, _D]),
 }
 

@@ -696,6 +696,71 @@ class GaussianRBFKernel(Kernel):
         self.kernel_parameters_ = [self.scale_matrix()]
 
 
+class InverseMultiquadricKernel(Kernel):
+    """Inverse multiquadric kernel (extension): k(x, x') = (1 + a |x-x'|²)^(-1/2),
+    ∇_x k = -a (x - x') k³; the exponent and the offset are fixed.
+
+    ScaleMethod.Median recomputes a = ln(N)/med² every step on the device (the
+    RBF kernel's median); ScaleMethod.Constant keeps the a given as `scale` or
+    set by UpdateParameters([a]).  Runs every step on the device like the
+    GaussianRBFKernel (svgd_set_kernel(SVGD_KERNEL_IMQ))."""
+
+    class ScaleMethod(enum.IntEnum):
+        Median = 0
+        Constant = 1
+
+    def __init__(self, coord_matrix, method=None, scale: float = 1.0):
+        method = InverseMultiquadricKernel.ScaleMethod.Median if method is None else method
+        super().__init__(np.asarray(coord_matrix).shape[0])
+        if method not in tuple(InverseMultiquadricKernel.ScaleMethod):
+            raise ValueError(PREFIX + "[Argument error] Invalid scale method Enum provided.")
+        self.scale_method_ = method
+        self.coord_matrix_ = coord_matrix
+        self.scale_ = self._checked(scale)
+        self.kernel_parameters_ = [np.float64(self.scale_)]
+        # the closed form as the kernel function too, so imq + k, imq * k, ...
+        # compose on the generic host path like any set kernel
+        self._fun = InverseMultiquadricKernel._value
+        self._grad = InverseMultiquadricKernel._gradient
+
+    @staticmethod
+    def _checked(a):
+        a = float(a)
+        if not (a >= 0.0) or not np.isfinite(a):
+            raise ValueError(PREFIX + "[Argument Error] The inverse multiquadric scale must be finite and >= 0.")
+        return a
+
+    @staticmethod
+    def _value(x, params, loc):  # a = params[0]
+        diff = np.asarray(x, dtype=np.float64) - loc
+        return float(1.0 / np.sqrt(1.0 + float(params[0]) * (diff @ diff)))
+
+    @staticmethod
+    def _gradient(x, params, loc):
+        diff = np.asarray(x, dtype=np.float64) - loc
+        a = float(params[0])
+        k = 1.0 / np.sqrt(1.0 + a * (diff @ diff))
+        return -a * diff * (k * k * k)
+
+    def EvaluateKernel(self, x):
+        return self._value(x, [self.scale_], self.location_)
+
+    def EvaluateKernelGrad(self, x):
+        return self._gradient(x, [self.scale_], self.location_)
+
+    def UpdateParameters(self, params):
+        a = np.asarray(params[0], dtype=np.float64)
+        if a.ndim != 0 and a.size != 1:
+            raise DimensionMismatchException("The inverse multiquadric kernel takes one scalar scale.")
+        self.scale_ = self._checked(a.reshape(-1)[0] if a.ndim else a)
+        self.kernel_parameters_ = [np.float64(self.scale_)]
+
+
+def _hessian_scale(kernel):
+    return (isinstance(kernel, GaussianRBFKernel)
+            and kernel.scale_method_ == GaussianRBFKernel.ScaleMethod.Hessian)
+
+
 # -------------------------------------------------------------- optimizers --
 
 class Optimizer:
@@ -904,6 +969,21 @@ class Context:
     def set_scale(self, method, a=1.0):
         self.check(self.lib.svgd_set_scale(self.h, method, a))
 
+    KERNELS = {"rbf": C.SVGD_KERNEL_RBF, "imq": C.SVGD_KERNEL_IMQ}
+
+    def set_kernel(self, kind):
+        """The kernel of phi and of every step (svgd_set_kernel): "rbf" (the
+        default) or "imq", the inverse multiquadric; every rank alike."""
+        if kind not in self.KERNELS:
+            raise ValueError(PREFIX + "[Argument Error] Invalid kernel kind.")
+        self.check(self.lib.svgd_set_kernel(self.h, self.KERNELS[kind]))
+
+    @property
+    def kernel(self):
+        k = ctypes.c_int()
+        self.check(self.lib.svgd_get_kernel(self.h, ctypes.byref(k)))
+        return {v: n for n, v in self.KERNELS.items()}[k.value]
+
     def median_scale(self):
         a, m = ctypes.c_double(), ctypes.c_double()
         self.check(self.lib.svgd_median_scale(self.h, ctypes.byref(a), ctypes.byref(m)))
@@ -1011,7 +1091,8 @@ class Context:
         self.check(self.lib.svgd_step(self.h, None))
 
     def ksd(self, G_shard=None, a=None, rows=False):
-        """Kernelized Stein discrepancy of the current particles (svgd_ksd):
+        """Kernelized Stein discrepancy of the current particles (svgd_ksd),
+        the RBF statistic whatever kernel is set:
         (KSD²_V, KSD²_U), with this rank's row_i = (1/N) Σ_j u_ij appended
         when rows=True.  G_shard: this rank's rows of ∇log p (None: the device
         model); a: the RBF scale (None: median_scale() of the particles)."""
@@ -1061,7 +1142,8 @@ class Context:
 class SVGD:
     """SVGD.hpp:84-511 on the MI355X path.
 
-    A GaussianRBFKernel runs every step on the device (UsesDevicePath()).  Any
+    A GaussianRBFKernel or an InverseMultiquadricKernel runs every step on the
+    device (UsesDevicePath()).  Any
     other kernel runs the reference's ComputePhi on the host (the generic
     kernel path, SURVEY 8(f) 4: SVGD.hpp:407-454 with the kernel's location
     at each x_i, then the optimizer's own Step and the clamp); the choice is
@@ -1119,7 +1201,7 @@ class SVGD:
         self.logs_ = []
         self.ctx = None
         self.device_ = kw.get("device", 0)
-        if isinstance(kernel, GaussianRBFKernel):
+        if isinstance(kernel, (GaussianRBFKernel, InverseMultiquadricKernel)):
             self.ctx = Context(self.dimension_, coord.shape[1], device=kw.get("device", 0))
         elif not hasattr(opt, "Step"):
             raise ValueError(PREFIX + "[Argument Error] Invalid Optimizer object pointer.")
@@ -1140,7 +1222,14 @@ class SVGD:
         c.set_optimizer(self.optimizer_.kind, *self.optimizer_.params())
         c.set_bounds(*(self.bounds_ if self.bounds_ is not None else (None, None)))
         k = self.kernel_
-        if k.scale_method_ == GaussianRBFKernel.ScaleMethod.Constant:
+        if isinstance(k, InverseMultiquadricKernel):
+            # (a scalar scale first: the IMQ kernel refuses a context on a matrix scale)
+            if k.scale_method_ == InverseMultiquadricKernel.ScaleMethod.Constant:
+                c.set_scale(C.SVGD_SCALE_FIXED, k.scale_)
+            else:
+                c.set_scale(C.SVGD_SCALE_MEDIAN, 0.0)
+            c.set_kernel("imq")
+        elif k.scale_method_ == GaussianRBFKernel.ScaleMethod.Constant:
             if k.scale_matrix_ is not None:
                 c.set_scale_matrix(k.scale_matrix_)
             else:
@@ -1153,18 +1242,17 @@ class SVGD:
             c.set_device_model(self.model_)
             self._device_batch = self.model_.batch_
         # a Hessian scale on the device step: the device model supplies the sum
-        c.set_device_hessian(self.UsesDeviceModelStep()
-                             and k.scale_method_ == GaussianRBFKernel.ScaleMethod.Hessian)
+        c.set_device_hessian(self.UsesDeviceModelStep() and _hessian_scale(k))
         self._initialized = True
 
     def UsesDeviceModelStep(self):
         """The whole step, grad log p included, runs on the device
         (svgd_step(ctx, NULL)): a model of exactly the built-in GLM type, an
-        RBF kernel on the device path -- with a Hessian scale only when the
+        RBF or IMQ kernel on the device path -- with a Hessian scale only when the
         kernel's target model is the stepped model, whose device mirror then
         supplies the Hessian sum too (svgd_set_device_hessian) -- and no
         matrix logging (which reads X_t and G from the host buffers)."""
-        hess = self.kernel_.scale_method_ == GaussianRBFKernel.ScaleMethod.Hessian
+        hess = _hessian_scale(self.kernel_)
         return (self.ctx is not None and type(self.model_) is GeneralizedLinearModel
                 and (not hess or self.kernel_.target_model_ is self.model_)
                 and not self.log_)
@@ -1181,7 +1269,7 @@ class SVGD:
             return
         c = self.ctx
         c.set_particles(np.ascontiguousarray(self.coord_matrix_.T))
-        hess = self.kernel_.scale_method_ == GaussianRBFKernel.ScaleMethod.Hessian
+        hess = _hessian_scale(self.kernel_)
         hmodel = self.kernel_.target_model_ if hess else None
         device_model = self.UsesDeviceModelStep()
         for _ in range(self.num_iterations_):
@@ -1288,8 +1376,15 @@ class SVGD:
         M = c.get_scale_matrix()
         K = np.empty((n, n))
         Kg = np.empty((d * n, n))
+        imq = isinstance(self.kernel_, InverseMultiquadricKernel)
         for i in range(n):
             diff = P - P[i]  # x_j - x_i
+            if imq:  # the class's closed form at the step's scale a (M = a I)
+                a = M[0, 0]
+                kv = 1.0 / np.sqrt(1.0 + a * np.einsum("jk,jk->j", diff, diff))
+                K[:, i] = kv
+                Kg[:, i] = (-a * diff * (kv ** 3)[:, None]).reshape(-1)
+                continue
             Md = diff @ M.T
             kv = np.exp(-np.einsum("jk,jk->j", diff, Md))
             K[:, i] = kv

@@ -3,7 +3,7 @@
 // One context = one GPU (one process per GPU in multi-GPU runs).  The context
 // owns every resource it allocates (resource.h): deleting it frees them all.
 // State that one unit alone reads or writes sits in that unit's group (co,
-// sym, ms, hs, tm, dm, ksd, pred); what several units share stays flat.  The units
+// sym, ms, hs, tm, dm, ksd, pred, imq); what several units share stays flat.  The units
 // (ctx_*.cpp, svgd_capi.cpp) call each other through the functions declared
 // at the end, per unit.
 #pragma once
@@ -296,6 +296,17 @@ struct svgd_ctx {
         std::vector<double> h_mat;
     } ms;
     bool have_particles = false;
+    // the kernel of phi (svgd_set_kernel) and the inverse multiquadric pass's
+    // work arrays (svgd_imq.h), allocated by the first svgd_set_kernel(IMQ): a
+    // context that never asks for it allocates and launches nothing of this
+    struct Imq {
+        int kind = SVGD_KERNEL_RBF;
+        bool ready = false;
+        int S = 1;                      // column-tile ranges of the pass
+        int64_t ldp = 0;
+        svgd_amd::DevBuf<double> rec;   // imq_padded(n) records of imq_rec_stride(d) doubles
+        svgd_amd::DevBuf<double> part;  // S x ldp x (2d+1) partial sums
+    } imq;
 
     // timing (svgd_set_timing): level 1 = phase events at the phase
     // boundaries only; level 2 adds the diagnostic events (phi kernel alone,
@@ -447,6 +458,8 @@ inline bool matrix_scale(const svgd_ctx *c)
 {
     return c->scale_method == SVGD_SCALE_MATRIX || c->scale_method == SVGD_SCALE_HESSIAN;
 }
+
+inline bool imq_kernel(const svgd_ctx *c) { return c->imq.kind == SVGD_KERNEL_IMQ; }
 
 inline bool has_device_model(const svgd_ctx *c) { return c->dm.k > 0 || c->dm.glm.m > 0; }
 

@@ -1,6 +1,8 @@
 // ctx_phi.cpp -- G's upload and all-gather, phi_hat on the planned path (with the
 // fused optimizer update) and the kernel scale's setters and getters.
 #include "ctx.h"
+#include "svgd_imq.h"
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 
@@ -46,6 +48,33 @@ int alloc_matrix_scale(svgd_ctx *c)
     CHK(dalloc(c, &c->ms.err, 1));
     HIPCHK(c, c->ms.h_err.alloc(1, hipHostMallocDefault));
     *c->ms.h_err = 0;
+    return SVGD_OK;
+}
+
+const char *const IMQ_SCALE_MSG =
+    "[Argument Error] The inverse multiquadric kernel takes a scalar scale (median or fixed), not a "
+    "Hessian or matrix scale.";
+
+// The IMQ pass's records and partials (the first svgd_set_kernel(IMQ)).
+// Column splits: the work-groups take equal time, so the grid (row groups x
+// S) should fill the device's resident slots a whole number of times, at most
+// twice (as svgd_set_device_glm sizes the score's splits).
+int alloc_imq(svgd_ctx *c)
+{
+    svgd_ctx::Imq &q = c->imq;
+    if (q.ready) return SVGD_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const int d = c->dim;
+    const int64_t groups = std::max<int64_t>(1, (c->nrows + IMQ_ROWS_PER_WG - 1) / IMQ_ROWS_PER_WG);
+    int cus = 0;
+    HIPCHK(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
+    const int64_t resident = (int64_t)std::max(1, cus) * imq_blocks_per_cu(d);
+    q.S = (int)std::min<int64_t>(std::max<int64_t>(1, 2 * resident / groups), imq_tiles(d, c->n));
+    q.ldp = std::max<int64_t>(1, c->nrows);
+    CHK(dalloc(c, &q.rec, imq_padded(c->n) * imq_rec_stride(d)));
+    CHK(dalloc(c, &q.part, (int64_t)q.S * q.ldp * imq_part_width(d)));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    q.ready = true;
     return SVGD_OK;
 }
 
@@ -128,6 +157,29 @@ int run_phi(svgd_ctx *c, const OptArgs *opt)
         c->co.gg_pending = false;
     }
     if (med_end) diag_end(c, c->stream, med_end, DG_PHI_WAIT, true);
+    // The inverse multiquadric kernel, chosen after the plan was made like a
+    // matrix scale, replaces the planned chain per call: records from this
+    // step's xc and the all-gathered G, the fp64 MFMA pass over this rank's
+    // rows against all N columns, the finish.  Nothing keyed on the planned
+    // path runs (no row halves, no symmetric exchange); the update is
+    // k_opt_update's (run_phi_opt).
+    if (imq_kernel(c)) {
+        c->hs.xhalf_ready = false;
+        const svgd_ctx::Imq &q = c->imq;
+        HIPCHK(c, launch_imq_prep(c->dim, c->xc, c->plan.KP, c->G, c->n, q.rec, c->stream));
+        hipEvent_t k0 = diag_begin(c, c->stream);
+        HIPCHK(c, launch_imq_pass(c->dim, q.rec, c->scal, c->row0, c->nrows, c->n, q.S, q.part, q.ldp,
+                                  c->stream));
+        diag_end(c, c->stream, k0, DG_PHI_KERNEL, true);
+        HIPCHK(c, launch_imq_finish(c->dim, q.rec, c->scal, c->row0, c->nrows, q.part, q.S, q.ldp,
+                                    1.0 / (double)c->n, c->phi, c->stream));
+        if (c->tm.timing) {
+            HIPCHK(c, hipEventRecord(ev.b, c->stream));
+            c->tm.ev_phi.push_back(ev);
+            c->phi_end = c->last_phi_end = ev.b;
+        }
+        return SVGD_OK;
+    }
     // A matrix scale, chosen after the plan was made, modifies the planned
     // launch per call (matrix_scale_plan): no symmetric pass, the 4-wave row
     // kernel (signature rows, sc_sgn), zc / zcf = L^T xc for xc / xcf, wv = 2 M xc.
@@ -284,7 +336,7 @@ int run_phi_opt(svgd_ctx *c)
         return fail(c, SVGD_ERR_ARG, "[Argument Error] Invalid Optimizer object pointer.");
     OptArgs o;
     CHK(opt_args(c, &o));
-    const bool fused = c->plan.fused();
+    const bool fused = c->plan.fused() && !imq_kernel(c); // (the IMQ finish writes phi alone)
     c->phi_end = nullptr;
     c->hs.xh_valid = false;
     CHK(run_phi(c, fused ? &o : nullptr));
@@ -317,6 +369,7 @@ int svgd_set_scale(svgd_ctx *c, int method, double fixed_a)
     CHK(resolve_pending(c));
     if (method != SVGD_SCALE_MEDIAN && method != SVGD_SCALE_FIXED && method != SVGD_SCALE_HESSIAN)
         return fail(c, SVGD_ERR_ARG, "[Argument error] Invalid scale method Enum provided.");
+    if (method == SVGD_SCALE_HESSIAN && imq_kernel(c)) return fail(c, SVGD_ERR_ARG, IMQ_SCALE_MSG);
     if (method == SVGD_SCALE_HESSIAN) CHK(alloc_matrix_scale(c));
     c->scale_method = method;
     c->fixed_a = fixed_a;
@@ -332,12 +385,36 @@ int svgd_set_scale_matrix(svgd_ctx *c, const double *M)
         for (int q = 0; q < r; ++q)
             if (M[r * d + q] != M[q * d + r])
                 return fail(c, SVGD_ERR_ARG, "[Argument Error] The kernel scale matrix must be symmetric.");
+    if (imq_kernel(c)) return fail(c, SVGD_ERR_ARG, IMQ_SCALE_MSG);
     CHK(resolve_pending(c));
     CHK(alloc_matrix_scale(c));
     HIPCHK(c, hipMemcpyAsync(c->ms.src, M, sizeof(double) * (size_t)d * d, hipMemcpyHostToDevice,
                              c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->scale_method = SVGD_SCALE_MATRIX;
+    return SVGD_OK;
+}
+
+int svgd_set_kernel(svgd_ctx *c, int kind)
+{
+    if (!c) return SVGD_ERR_ARG;
+    if (kind != SVGD_KERNEL_RBF && kind != SVGD_KERNEL_IMQ)
+        return fail(c, SVGD_ERR_ARG, "[Argument Error] Invalid kernel kind.");
+    CHK(resolve_pending(c));
+    if (kind == SVGD_KERNEL_IMQ) {
+        if (matrix_scale(c)) return fail(c, SVGD_ERR_ARG, IMQ_SCALE_MSG);
+        if (c->dim > 64)
+            return fail(c, SVGD_ERR_ARG, "[Argument Error] The inverse multiquadric kernel supports d <= 64.");
+        CHK(alloc_imq(c));
+    }
+    c->imq.kind = kind;
+    return SVGD_OK;
+}
+
+int svgd_get_kernel(const svgd_ctx *c, int *kind)
+{
+    if (!c || !kind) return SVGD_ERR_ARG;
+    *kind = c->imq.kind;
     return SVGD_OK;
 }
 

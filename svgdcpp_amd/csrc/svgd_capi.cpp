@@ -10,6 +10,7 @@
 // The context and its units: ctx.h.
 #include "ctx.h"
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 
 using namespace svgd_amd;
@@ -251,6 +252,10 @@ int svgd_sync(svgd_ctx *c)
 int svgd_phi_kernel_name(const svgd_ctx *c, char *buf, int cap)
 {
     if (!c || !buf || cap <= 0) return SVGD_ERR_ARG;
+    if (imq_kernel(c)) { // (chosen after the plan too, but a kernel of its own)
+        std::snprintf(buf, (size_t)cap, "k_imq_pass<%d>", (c->dim + 3) / 4 * 4);
+        return SVGD_OK;
+    }
     phi_plan_name(c->plan, built_caps(c->dim, c->dtype), buf, cap);
     return SVGD_OK;
 }

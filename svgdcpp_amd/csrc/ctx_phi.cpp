@@ -90,6 +90,11 @@ int upload_g_begin(svgd_ctx *c, const double *G_shard)
             HIPCHK(c, hipEventSynchronize(c->ev_g)); // the previous upload left h_g
             std::memcpy(c->h_g, G_shard, bytes);
         }
+        // the last phi chain may still read G on the compute stream: a step
+        // returns with it queued, and a redo (resolve_pending) inside this
+        // very call has just queued one that needs the failed step's G
+        hipEvent_t xev = c->ev_xready_use ? c->ev_xready_use : c->ev_xready;
+        if (hipEventQuery(xev) != hipSuccess) HIPCHK(c, hipStreamWaitEvent(c->cstream, xev, 0));
         HIPCHK(c, hipMemcpyAsync(c->G + (size_t)c->row0 * c->dim, c->h_g, bytes,
                                  hipMemcpyHostToDevice, c->cstream));
     }

@@ -92,8 +92,14 @@ int svgd_set_bounds(svgd_ctx *c, const double *lower, const double *upper)
     }
     if (!lower || !upper)
         return fail(c, SVGD_ERR_DIM, "[Dimension Error] The provided bounds have incorrect dimensions.");
-    HIPCHK(c, hipMemcpy(c->lower, lower, sizeof(double) * c->dim, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->upper, upper, sizeof(double) * c->dim, hipMemcpyHostToDevice));
+    // the step just issued may not have read its bounds yet (its chain runs
+    // on c->stream, which the null stream does not wait for): drain it, then
+    // upload in stream order like every other setter
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->lower, lower, sizeof(double) * c->dim, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->upper, upper, sizeof(double) * c->dim, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream)); // the caller's arrays may be reused
     c->bounded = true;
     return SVGD_OK;
 }

@@ -316,6 +316,58 @@ public:
         return unbiased ? u : v;
     }
 
+    /** Extension: the same with the kernel of the statistic named:
+     *  SVGD_KERNEL_RBF is ComputeKSD(unbiased) whatever kernel this SVGD
+     *  steps with, SVGD_KERNEL_IMQ the inverse multiquadric statistic
+     *  (svgd_ksd_kernel).  The IMQ scale a is the kernel's own for an
+     *  InverseMultiquadricKernel with a Constant scale, else ln N / med^2 of
+     *  the particles. */
+    double ComputeKSD(bool unbiased, int kernel)
+    {
+        if (kernel == SVGD_KERNEL_RBF)
+            return ComputeKSD(unbiased);
+        if (kernel != SVGD_KERNEL_IMQ)
+            throw std::invalid_argument(SVGDCPP_LOG_PREFIX + "[Argument Error] Unknown KSD kernel.");
+        std::shared_ptr<svgd_ctx> tmp;
+        svgd_ctx *c = ctx_.get();
+        int64_t r0 = row0_, r1 = row1_;
+        if (!c)
+        {
+            const int rc = svgd_create(&c, dimension_, (int64_t)num_particles_, SVGD_F64, device_);
+            tmp.reset(c, [](svgd_ctx *p) { svgd_destroy(p); });
+            if (rc != SVGD_OK)
+                svgdcpp::ThrowFromCode(rc, svgd_last_error(c));
+            r0 = 0;
+            r1 = (int64_t)num_particles_;
+        }
+        auto check = [&](int rc) {
+            if (rc != SVGD_OK)
+                svgdcpp::ThrowFromCode(rc, svgd_last_error(c));
+        };
+        const double *X = coord_matrix_ptr_->data();
+        check(svgd_set_particles(c, X));
+        // the device score when this context mirrors the model (Initialize)
+        const bool device_score = c == ctx_.get() && initialized_ && UsesDeviceModelStep();
+        std::vector<double> G((size_t)std::max<int64_t>(1, r1 - r0) * dimension_);
+        if (!device_score)
+            model_ptr_->LogModelGradBatch(X + (size_t)r0 * dimension_, r1 - r0, G.data());
+        double a = 0.0;
+        if (imq_ptr_ && imq_ptr_->GetScaleMethod() == InverseMultiquadricKernel::ScaleMethod::Constant)
+            a = imq_ptr_->GetScale();
+        else
+            check(svgd_median_scale(c, &a, nullptr));
+        double v = 0.0, u = 0.0;
+        if (device_score)
+        {
+            const GeneralizedLinearModel &glm = static_cast<const GeneralizedLinearModel &>(*model_ptr_);
+            check(svgd_set_device_glm_batch(c, glm.BatchBegin(), glm.BatchCount()));
+            device_m0_ = glm.BatchBegin();
+            device_count_ = glm.BatchCount();
+        }
+        check(svgd_ksd_kernel(c, SVGD_KERNEL_IMQ, device_score ? nullptr : G.data(), a, &v, &u, nullptr));
+        return unbiased ? u : v;
+    }
+
     /** What Predict returns: per test row the predictive mean, its variance
      *  over the particles and (with labels, else empty) the log predictive
      *  density. */

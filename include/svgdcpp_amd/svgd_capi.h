@@ -422,11 +422,35 @@ int svgd_ksd(svgd_ctx *ctx, const double *G_shard, double a, double *ksd2_v, dou
  * (the median stays the dtype's), the optimizer update is a launch of its
  * own, and two calls on the same state return the same bits.
  * svgd_phi_kernel_name reports the IMQ pass while it is set.  svgd_ksd stays
- * the RBF statistic whatever kernel is set.  d <= 64. */
+ * the RBF statistic whatever kernel is set; svgd_ksd_kernel (below) gives the
+ * IMQ one.  d <= 64. */
 #define SVGD_KERNEL_RBF 0
 #define SVGD_KERNEL_IMQ 1
 int svgd_set_kernel(svgd_ctx *ctx, int kind);
 int svgd_get_kernel(const svgd_ctx *ctx, int *kind);
+
+/* Kernelized Stein discrepancy with the kernel named in the call, whatever
+ * kernel the context steps with (svgd_set_kernel neither reads nor is read
+ * by it).  SVGD_KERNEL_RBF is svgd_ksd itself: the same code, the same bits.
+ * SVGD_KERNEL_IMQ: with q = 1 + a |r|^2, k = q^(-1/2), r = x_i - x_j,
+ *   u_ij   = k s_i.s_j + a k^3 (s_i - s_j).r + a d k^3 - 3 a^2 k^5 |r|^2
+ *   u_ii   = |s_i|^2 + a d
+ * and row_i, KSD2_V, KSD2_U as for svgd_ksd (Gorham & Mackey 2017 with
+ * beta = -1/2, c = 1).  The contract is svgd_ksd's: G_shard == NULL evaluates
+ * the device model, any output may be NULL, fp64 whatever the dtype, equal
+ * bits on equal state, a pure observer with work arrays of its own
+ * (allocated by the first IMQ call), collective in multi-GPU mode.  a must be
+ * finite and > 0 and the kernel one of the two (SVGD_ERR_ARG).  d <= 64. */
+int svgd_ksd_kernel(svgd_ctx *ctx, int kernel, const double *G_shard, double a, double *ksd2_v,
+                    double *ksd2_u, double *rows_shard_out);
+/* host, no GPU: the same two statistics of X (n x dim) with scores G
+ * (n x dim) by direct differences (no centring, no Gram form); rows_out
+ * (n, may be NULL) takes row_i.  OpenMP over rows, each row's sum in particle
+ * order and the sums over rows in row order (independent of the thread
+ * count).  Refused: NULL X or G, an unknown kernel, a not finite or <= 0
+ * (SVGD_ERR_ARG); dim < 1 or n < 1 (SVGD_ERR_DIM). */
+int svgd_ksd_host(int kernel, int dim, int64_t n, const double *X, const double *G, double a,
+                  double *ksd2_v, double *ksd2_u, double *rows_out);
 /* host, no GPU: phi_out (nrows x dim) = phi_i of the definition above for the
  * rows [row0, row0 + nrows) of X (n x dim) with G (n x dim), by direct
  * differences; OpenMP over rows, each row's sums in particle order

@@ -91,6 +91,8 @@ SIGNATURES = {
     "svgd_set_device_model": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "svgd_device_logp_grad": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]),
     "svgd_ksd": (ctypes.c_int, [_P, _D, ctypes.c_double, _D, _D, _D]),
+    "svgd_ksd_kernel": (ctypes.c_int, [_P, ctypes.c_int, _D, ctypes.c_double, _D, _D, _D]),
+    "svgd_ksd_host": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _I64, _D, _D, ctypes.c_double, _D, _D, _D]),
     "svgd_plan_rows": (None, [_I64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
     "svgd_plan_phi_name": (ctypes.c_int, [ctypes.c_int, _I64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                           ctypes.c_char_p, ctypes.c_int]),

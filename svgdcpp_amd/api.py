@@ -1090,12 +1090,17 @@ class Context:
     def step_device(self):
         self.check(self.lib.svgd_step(self.h, None))
 
-    def ksd(self, G_shard=None, a=None, rows=False):
-        """Kernelized Stein discrepancy of the current particles (svgd_ksd),
-        the RBF statistic whatever kernel is set:
+    def ksd(self, G_shard=None, a=None, rows=False, kernel="rbf"):
+        """Kernelized Stein discrepancy of the current particles, with the
+        kernel named here whatever kernel the context steps with: "rbf"
+        (svgd_ksd) or "imq" / SVGD_KERNEL_IMQ (svgd_ksd_kernel, the inverse
+        multiquadric with the exponent -1/2):
         (KSD²_V, KSD²_U), with this rank's row_i = (1/N) Σ_j u_ij appended
         when rows=True.  G_shard: this rank's rows of ∇log p (None: the device
-        model); a: the RBF scale (None: median_scale() of the particles)."""
+        model); a: the kernel scale (None: median_scale() of the particles)."""
+        kind = self.KERNELS.get(kernel, kernel) if isinstance(kernel, str) else kernel
+        if kind not in (C.SVGD_KERNEL_RBF, C.SVGD_KERNEL_IMQ):
+            raise ValueError(PREFIX + "[Argument Error] Invalid kernel kind.")
         if a is None:
             a = self.median_scale()[0]
         G = None if G_shard is None else np.ascontiguousarray(G_shard, dtype=np.float64)
@@ -1103,8 +1108,12 @@ class Context:
             raise DimensionMismatchException("Log-gradient shard has incorrect dimensions.")
         v, u = ctypes.c_double(), ctypes.c_double()
         out = np.empty(self.row1 - self.row0) if rows else None
-        self.check(self.lib.svgd_ksd(self.h, C.dptr(G), float(a), ctypes.byref(v), ctypes.byref(u),
-                                     C.dptr(out)))
+        if kind == C.SVGD_KERNEL_RBF:
+            self.check(self.lib.svgd_ksd(self.h, C.dptr(G), float(a), ctypes.byref(v), ctypes.byref(u),
+                                         C.dptr(out)))
+        else:
+            self.check(self.lib.svgd_ksd_kernel(self.h, int(kind), C.dptr(G), float(a), ctypes.byref(v),
+                                                ctypes.byref(u), C.dptr(out)))
         return (v.value, u.value, out) if rows else (v.value, u.value)
 
     def glm_predict(self, A, y=None, link="logistic", lik_scale=1.0):
@@ -1300,23 +1309,33 @@ class SVGD:
         self.coord_matrix_[...] = X.T
         self._write_logs()
 
-    def ComputeKSD(self, unbiased=False):
+    def ComputeKSD(self, unbiased=False, kernel=None):
         """KSD² of the caller's coordinate matrix against the model (extension):
-        the V-statistic, or the U-statistic when unbiased.  The RBF scale is
-        the kernel's own for an isotropic ScaleMethod.Constant, else
-        ln N / med² of the current particles.  The generic host-kernel path
-        opens a context on the configured device for the call."""
+        the V-statistic, or the U-statistic when unbiased.  kernel: None or
+        "rbf" is the RBF statistic (whatever kernel the SVGD steps with),
+        "imq" the inverse multiquadric one.  The scale is the SVGD's kernel's
+        own where that kernel is of the statistic's kind with an isotropic
+        ScaleMethod.Constant, else ln N / med² of the current particles.  The
+        generic host-kernel path opens a context on the configured device for
+        the call."""
+        kind = "rbf" if kernel is None else kernel
+        if kind not in Context.KERNELS:
+            raise ValueError(PREFIX + "[Argument Error] Invalid kernel kind.")
         P = np.ascontiguousarray(np.asarray(self.coord_matrix_, dtype=np.float64).T)
         G = self.model_.log_model_grad(P)
         k = self.kernel_
         a = None
-        if (isinstance(k, GaussianRBFKernel) and k.scale_matrix_ is None
-                and k.scale_method_ == GaussianRBFKernel.ScaleMethod.Constant):
+        if kind == "rbf":
+            if (isinstance(k, GaussianRBFKernel) and k.scale_matrix_ is None
+                    and k.scale_method_ == GaussianRBFKernel.ScaleMethod.Constant):
+                a = k.scale_
+        elif (isinstance(k, InverseMultiquadricKernel)
+                and k.scale_method_ == InverseMultiquadricKernel.ScaleMethod.Constant):
             a = k.scale_
         c = self.ctx if self.ctx is not None else Context(P.shape[1], P.shape[0], device=self.device_)
         try:
             c.set_particles(P)
-            v, u = c.ksd(G[c.row0:c.row1], a)
+            v, u = c.ksd(G[c.row0:c.row1], a, kernel=kind)
         finally:
             if c is not self.ctx:
                 c.close()

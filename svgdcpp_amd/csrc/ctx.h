@@ -3,7 +3,7 @@
 // One context = one GPU (one process per GPU in multi-GPU runs).  The context
 // owns every resource it allocates (resource.h): deleting it frees them all.
 // State that one unit alone reads or writes sits in that unit's group (co,
-// sym, ms, hs, tm, dm, ksd, pred, imq); what several units share stays flat.  The units
+// sym, ms, hs, tm, dm, ksd, ksdq, pred, imq); what several units share stays flat.  The units
 // (ctx_*.cpp, svgd_capi.cpp) call each other through the functions declared
 // at the end, per unit.
 #pragma once
@@ -392,6 +392,19 @@ struct svgd_ctx {
         svgd_amd::DevBuf<double> nrm, cvec, diag;
         svgd_amd::DevBuf<double> part, rows, bpart, out;
     } ksd;
+
+    // svgd_ksd_kernel(SVGD_KERNEL_IMQ)'s own work arrays (allocated by its
+    // first call): the same observer under the inverse multiquadric kernel;
+    // nothing of the imq group (the phi records) is read or written
+    struct KsdImq {
+        bool ready = false;
+        int64_t ldp = 0;
+        int S = 1;                                   // column-tile ranges of the pass
+        svgd_amd::DevBuf<double> G;                  // world*chunk x d (all-gathered scores)
+        svgd_amd::DevBuf<double> mu, mpart;          // centre, its column-sum partials
+        svgd_amd::DevBuf<double> rec, diag;          // ksd_imq_padded(n) records, |s|^2 + ad
+        svgd_amd::DevBuf<double> part, rows, bpart, out;
+    } ksdq;
 
     // svgd_glm_predict's own work arrays (allocated by its first call, grown
     // when a call brings more records): it reads X and nothing else of the

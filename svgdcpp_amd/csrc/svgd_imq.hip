@@ -35,6 +35,7 @@
 
 #include "dispatch.h"
 #include "svgd_imq.h"
+#include "svgd_imq_dev.h" // rsqrt_full
 
 namespace svgd_amd {
 namespace imq {
@@ -57,19 +58,6 @@ template <int KP> struct Geom {
     static constexpr int NPRE = (NP + NT - 1) / NT; // per-thread prefetch registers
     static constexpr int LDS = 2 * TW * 8;          // two tile buffers
 };
-
-// s^(-1/2) for 1 <= s <= 1e300, to fp64 rounding: the hardware seed, one
-// third-order step and one Newton step, each on the residual e = 1 - s y^2
-// (the second step leaves a seed of relative error as large as 1e-4 below
-// 1e-16); no division
-__device__ __forceinline__ double rsqrt_full(double s)
-{
-    double y = __builtin_amdgcn_rsq(s);
-    double e = fma(-(s * y), y, 1.0);
-    y = fma(y * e, fma(0.375, e, 0.5), y);
-    e = fma(-(s * y), y, 1.0);
-    return fma(0.5 * y, e, y);
-}
 
 __global__ __launch_bounds__(256) void k_imq_prep(const double *__restrict__ xc, int xs,
                                                   const double *__restrict__ G, int d, int KP, int RS,

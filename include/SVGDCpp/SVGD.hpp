@@ -368,6 +368,78 @@ public:
         return unbiased ? u : v;
     }
 
+    /** What Thin returns: the chosen particles as columns (d x m), their
+     *  column indices in the coordinate matrix in pick order (they may
+     *  repeat) and ksd2[t - 1] = KSD^2_V of the first t picks. */
+    struct Thinned
+    {
+        Eigen::MatrixXd points;
+        std::vector<int64_t> index;
+        Eigen::VectorXd ksd2;
+    };
+
+    /** Extension: Stein thinning of the caller's coordinate matrix against
+     *  the model (svgd_stein_thin on the device): the m greedily chosen
+     *  particles whose empirical measure has the smallest KSD under the
+     *  kernel named (SVGD_KERNEL_IMQ or SVGD_KERNEL_RBF).  The context, the
+     *  score and the scale a are handled as in ComputeKSD; in a sharded run
+     *  every rank calls it and gets the same result. */
+    Thinned Thin(int64_t m, int kernel = SVGD_KERNEL_IMQ)
+    {
+        if (kernel != SVGD_KERNEL_RBF && kernel != SVGD_KERNEL_IMQ)
+            throw std::invalid_argument(SVGDCPP_LOG_PREFIX + "[Argument Error] Unknown Stein thinning kernel.");
+        if (m < 1)
+            throw std::invalid_argument(SVGDCPP_LOG_PREFIX + "[Argument Error] Stein thinning needs at least one pick.");
+        std::shared_ptr<svgd_ctx> tmp;
+        svgd_ctx *c = ctx_.get();
+        int64_t r0 = row0_, r1 = row1_;
+        if (!c)
+        {
+            const int rc = svgd_create(&c, dimension_, (int64_t)num_particles_, SVGD_F64, device_);
+            tmp.reset(c, [](svgd_ctx *p) { svgd_destroy(p); });
+            if (rc != SVGD_OK)
+                svgdcpp::ThrowFromCode(rc, svgd_last_error(c));
+            r0 = 0;
+            r1 = (int64_t)num_particles_;
+        }
+        auto check = [&](int rc) {
+            if (rc != SVGD_OK)
+                svgdcpp::ThrowFromCode(rc, svgd_last_error(c));
+        };
+        const double *X = coord_matrix_ptr_->data();
+        check(svgd_set_particles(c, X));
+        // the device score when this context mirrors the model (Initialize)
+        const bool device_score = c == ctx_.get() && initialized_ && UsesDeviceModelStep();
+        std::vector<double> G((size_t)std::max<int64_t>(1, r1 - r0) * dimension_);
+        if (!device_score)
+            model_ptr_->LogModelGradBatch(X + (size_t)r0 * dimension_, r1 - r0, G.data());
+        double a = 0.0;
+        if (kernel == SVGD_KERNEL_IMQ && imq_ptr_ &&
+            imq_ptr_->GetScaleMethod() == InverseMultiquadricKernel::ScaleMethod::Constant)
+            a = imq_ptr_->GetScale();
+        else if (kernel == SVGD_KERNEL_RBF && rbf_ptr_ &&
+                 rbf_ptr_->GetScaleMethod() == GaussianRBFKernel::ScaleMethod::Constant && rbf_ptr_->IsIsotropic())
+            a = rbf_ptr_->GetScale();
+        else
+            check(svgd_median_scale(c, &a, nullptr));
+        if (device_score)
+        {
+            const GeneralizedLinearModel &glm = static_cast<const GeneralizedLinearModel &>(*model_ptr_);
+            check(svgd_set_device_glm_batch(c, glm.BatchBegin(), glm.BatchCount()));
+            device_m0_ = glm.BatchBegin();
+            device_count_ = glm.BatchCount();
+        }
+        Thinned out;
+        out.index.resize((size_t)m);
+        out.ksd2.resize(m);
+        check(svgd_stein_thin(c, kernel, device_score ? nullptr : G.data(), a, m, out.index.data(), out.ksd2.data()));
+        out.points.resize(dimension_, m);
+        for (int64_t t = 0; t < m; ++t)
+            for (long r = 0; r < (long)dimension_; ++r)
+                out.points(r, t) = (*coord_matrix_ptr_)(r, out.index[(size_t)t]);
+        return out;
+    }
+
     /** What Predict returns: per test row the predictive mean, its variance
      *  over the particles and (with labels, else empty) the log predictive
      *  density. */

@@ -451,6 +451,37 @@ int svgd_ksd_kernel(svgd_ctx *ctx, int kernel, const double *G_shard, double a, 
  * (SVGD_ERR_ARG); dim < 1 or n < 1 (SVGD_ERR_DIM). */
 int svgd_ksd_host(int kernel, int dim, int64_t n, const double *X, const double *G, double a,
                   double *ksd2_v, double *ksd2_u, double *rows_out);
+/* Stein thinning (Riabiz et al. 2022): the greedy choice of m of the current
+ * particles whose empirical measure has the smallest KSD under the kernel
+ * named in the call, with u_ij and u_ii as above for svgd_ksd /
+ * svgd_ksd_kernel (u_ii = |s_i|^2 + 2ad for the RBF kernel):
+ *   acc_0[j] = 0
+ *   for t = 1..m:
+ *     obj_t[j] = u_jj / 2 + acc_{t-1}[j]              j = 0..N-1
+ *     pi_t     = the smallest j that attains min_j obj_t[j]
+ *     S_t      = S_{t-1} + 2 acc_{t-1}[pi_t] + u_{pi_t pi_t}      (S_0 = 0)
+ *     ksd2_t   = S_t / t^2        (= KSD2_V of the multiset {pi_1..pi_t})
+ *     acc_t[j] = acc_{t-1}[j] + u(pi_t, j)            (u(pi_t, pi_t) by index)
+ * Picks may repeat, so m may exceed N.  idx_out (m, may be NULL) takes the
+ * global row indices in pick order, ksd2_out (m, may be NULL) the ksd2_t.
+ * The contract is svgd_ksd_kernel's: G_shard == NULL evaluates the device
+ * model, fp64 whatever the dtype, blind to svgd_set_kernel, equal bits on
+ * equal state, a pure observer with work arrays of its own (allocated by the
+ * first call, grown when a later m needs it).  Collective in multi-GPU mode:
+ * each rank passes its rows of G, the selection runs on every rank on the
+ * all-gathered X and G, and every rank gets the same m indices and values.
+ * SVGD_ERR_ARG: an unknown kernel, a not finite or <= 0, m < 1, NULL G_shard
+ * without a device model, d > 64.  SVGD_ERR_RUNTIME: a ksd2_t that is not
+ * finite (the outputs are written). */
+int svgd_stein_thin(svgd_ctx *ctx, int kernel, const double *G_shard, double a, int64_t m,
+                    int64_t *idx_out, double *ksd2_out);
+/* host, no GPU: the same selection of X (n x dim) with scores G (n x dim) by
+ * direct differences, OpenMP over j inside a pick, the minimum compared in
+ * index order (independent of the thread count).  Refused: NULL X or G, an
+ * unknown kernel, a not finite or <= 0, m < 1 (SVGD_ERR_ARG); dim < 1 or
+ * n < 1 (SVGD_ERR_DIM); SVGD_ERR_RUNTIME as above. */
+int svgd_stein_thin_host(int kernel, int dim, int64_t n, const double *X, const double *G, double a,
+                         int64_t m, int64_t *idx_out, double *ksd2_out);
 /* host, no GPU: phi_out (nrows x dim) = phi_i of the definition above for the
  * rows [row0, row0 + nrows) of X (n x dim) with G (n x dim), by direct
  * differences; OpenMP over rows, each row's sums in particle order

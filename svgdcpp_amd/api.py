@@ -1116,6 +1116,32 @@ class Context:
                                                 ctypes.byref(u), C.dptr(out)))
         return (v.value, u.value, out) if rows else (v.value, u.value)
 
+    def stein_thin(self, m, G_shard=None, a=None, kernel="imq", trace=False):
+        """Stein thinning of the current particles (svgd_stein_thin;
+        collective): the global row indices of the m greedily chosen points
+        whose empirical measure has the smallest KSD under `kernel` ("imq" or
+        "rbf", whatever kernel the context steps with), in pick order (int64;
+        picks may repeat), and with trace=True also ksd2 (m), the KSD²_V of
+        the first t picks.  G_shard: this rank's rows of ∇log p (None: the
+        device model); a: the kernel scale (None: median_scale() of the
+        particles)."""
+        kind = self.KERNELS.get(kernel, kernel) if isinstance(kernel, str) else kernel
+        if kind not in (C.SVGD_KERNEL_RBF, C.SVGD_KERNEL_IMQ):
+            raise ValueError(PREFIX + "[Argument Error] Invalid kernel kind.")
+        m = int(m)
+        if m < 1:
+            raise ValueError(PREFIX + "[Argument Error] Stein thinning needs at least one pick.")
+        if a is None:
+            a = self.median_scale()[0]
+        G = None if G_shard is None else np.ascontiguousarray(G_shard, dtype=np.float64)
+        if G is not None and G.shape != (self.row1 - self.row0, self.dim):
+            raise DimensionMismatchException("Log-gradient shard has incorrect dimensions.")
+        idx = np.empty(m, dtype=np.int64)
+        ksd2 = np.empty(m) if trace else None
+        self.check(self.lib.svgd_stein_thin(self.h, int(kind), C.dptr(G), float(a), m,
+                                            idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), C.dptr(ksd2)))
+        return (idx, ksd2) if trace else idx
+
     def glm_predict(self, A, y=None, link="logistic", lik_scale=1.0):
         """Posterior predictive of a GLM on held-out rows A (m, d), labels y
         (m) optional, over the current particles of all ranks, on the device
@@ -1340,6 +1366,36 @@ class SVGD:
             if c is not self.ctx:
                 c.close()
         return u if unbiased else v
+
+    def Thin(self, m, kernel="imq"):
+        """Stein thinning of the caller's coordinate matrix against the model
+        (extension; svgd_stein_thin on the device): (points, idx, ksd2) with
+        points = the coordinate matrix's columns at idx (d, m), idx the m
+        picks in order (they may repeat) and ksd2[t - 1] the KSD²_V of the
+        first t picks.  The model's score and the scale are handled as in
+        ComputeKSD; the generic host-kernel path opens a context on the
+        configured device for the call."""
+        if kernel not in Context.KERNELS:
+            raise ValueError(PREFIX + "[Argument Error] Invalid kernel kind.")
+        P = np.ascontiguousarray(np.asarray(self.coord_matrix_, dtype=np.float64).T)
+        G = self.model_.log_model_grad(P)
+        k = self.kernel_
+        a = None
+        if kernel == "rbf":
+            if (isinstance(k, GaussianRBFKernel) and k.scale_matrix_ is None
+                    and k.scale_method_ == GaussianRBFKernel.ScaleMethod.Constant):
+                a = k.scale_
+        elif (isinstance(k, InverseMultiquadricKernel)
+                and k.scale_method_ == InverseMultiquadricKernel.ScaleMethod.Constant):
+            a = k.scale_
+        c = self.ctx if self.ctx is not None else Context(P.shape[1], P.shape[0], device=self.device_)
+        try:
+            c.set_particles(P)
+            idx, ksd2 = c.stein_thin(m, G[c.row0:c.row1], a, kernel=kernel, trace=True)
+        finally:
+            if c is not self.ctx:
+                c.close()
+        return np.ascontiguousarray(P[idx].T), idx, ksd2
 
     def Predict(self, A, y=None):
         """Posterior predictive of the GeneralizedLinearModel on held-out rows

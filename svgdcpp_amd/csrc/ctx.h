@@ -3,7 +3,7 @@
 // One context = one GPU (one process per GPU in multi-GPU runs).  The context
 // owns every resource it allocates (resource.h): deleting it frees them all.
 // State that one unit alone reads or writes sits in that unit's group (co,
-// sym, ms, hs, tm, dm, ksd, ksdq, pred, imq); what several units share stays flat.  The units
+// sym, ms, hs, tm, dm, ksd, ksdq, thin, pred, imq); what several units share stays flat.  The units
 // (ctx_*.cpp, svgd_capi.cpp) call each other through the functions declared
 // at the end, per unit.
 #pragma once
@@ -405,6 +405,21 @@ struct svgd_ctx {
         svgd_amd::DevBuf<double> rec, diag;          // ksd_imq_padded(n) records, |s|^2 + ad
         svgd_amd::DevBuf<double> part, rows, bpart, out;
     } ksdq;
+
+    // svgd_stein_thin's own work arrays (allocated by its first call, idx and S
+    // grown when a call asks for more picks): the selection reads X and
+    // nothing else of the step's state
+    struct Thin {
+        bool ready = false;
+        int64_t m_cap = 0;
+        svgd_amd::DevBuf<double> G;          // world*chunk x d (all-gathered scores)
+        svgd_amd::DevBuf<double> xs;         // 2d x thin_padded(n): x and s, coordinate-major
+        svgd_amd::DevBuf<double> diag, acc;  // thin_padded(n)
+        svgd_amd::DevBuf<double> pval;       // thin_part_slots(n) work-group minima ...
+        svgd_amd::DevBuf<int> pidx;          // ... and their indices
+        svgd_amd::DevBuf<int64_t> idx;       // m_cap picks
+        svgd_amd::DevBuf<double> S;          // m_cap running sums
+    } thin;
 
     // svgd_glm_predict's own work arrays (allocated by its first call, grown
     // when a call brings more records): it reads X and nothing else of the

@@ -410,6 +410,7 @@ Knobs read_knobs()
     get("SVGD_DEBUG_COLL", onoff, &k.debug_coll);
     get("SVGD_G_COMM", onoff, &k.g_comm);
     get("SVGD_HOSTCOMM", [](const char *e) { return std::string(e); }, &k.hostcomm);
+    get("SVGD_THIN_SELECT", onoff, &k.thin_select);
     return k;
 }
 

@@ -42,6 +42,7 @@ struct Knobs {
     Knob<int> host_threads;        // >= 1
     Knob<int> debug_coll, g_comm;  // on / off
     Knob<std::string> hostcomm;    // the shared-memory name
+    Knob<int> thin_select;         // on / off: Stein thinning's two-launch pick
 };
 
 // Which kernel computes phi_hat for a context's rows.

@@ -368,6 +368,48 @@ public:
         return unbiased ? u : v;
     }
 
+    /** Extension: the maximum mean discrepancy MMD^2 between the caller's
+     *  coordinate matrix and the sample Y (d x M, columns are points like the
+     *  coordinate matrix) under the kernel named (svgd_mmd on the device):
+     *  the biased V-statistic (>= 0 up to rounding), or the unbiased
+     *  U-statistic.  The context and the scale a are handled as in
+     *  ComputeKSD(bool, int); in a sharded run every rank calls it with the
+     *  same Y. */
+    double ComputeMMD(const Eigen::MatrixXd &Y, bool unbiased = false, int kernel = SVGD_KERNEL_RBF)
+    {
+        if (kernel != SVGD_KERNEL_RBF && kernel != SVGD_KERNEL_IMQ)
+            throw std::invalid_argument(SVGDCPP_LOG_PREFIX + "[Argument Error] Unknown MMD kernel.");
+        if (Y.rows() != (long)dimension_)
+            throw DimensionMismatchException("MMD sample does not match the dimension.");
+        std::shared_ptr<svgd_ctx> tmp;
+        svgd_ctx *c = ctx_.get();
+        if (!c)
+        {
+            const int rc = svgd_create(&c, dimension_, (int64_t)num_particles_, SVGD_F64, device_);
+            tmp.reset(c, [](svgd_ctx *p) { svgd_destroy(p); });
+            if (rc != SVGD_OK)
+                svgdcpp::ThrowFromCode(rc, svgd_last_error(c));
+        }
+        auto check = [&](int rc) {
+            if (rc != SVGD_OK)
+                svgdcpp::ThrowFromCode(rc, svgd_last_error(c));
+        };
+        check(svgd_set_particles(c, coord_matrix_ptr_->data()));
+        double a = 0.0;
+        if (kernel == SVGD_KERNEL_IMQ && imq_ptr_ &&
+            imq_ptr_->GetScaleMethod() == InverseMultiquadricKernel::ScaleMethod::Constant)
+            a = imq_ptr_->GetScale();
+        else if (kernel == SVGD_KERNEL_RBF && rbf_ptr_ &&
+                 rbf_ptr_->GetScaleMethod() == GaussianRBFKernel::ScaleMethod::Constant && rbf_ptr_->IsIsotropic())
+            a = rbf_ptr_->GetScale();
+        else
+            check(svgd_median_scale(c, &a, nullptr));
+        // (column-major d x M = row-major M x d: the points are contiguous)
+        double v = 0.0, u = 0.0;
+        check(svgd_mmd(c, kernel, Y.data(), (int64_t)Y.cols(), a, &v, &u, nullptr, nullptr));
+        return unbiased ? u : v;
+    }
+
     /** What Thin returns: the chosen particles as columns (d x m), their
      *  column indices in the coordinate matrix in pick order (they may
      *  repeat) and ksd2[t - 1] = KSD^2_V of the first t picks. */

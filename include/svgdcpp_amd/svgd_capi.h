@@ -451,6 +451,37 @@ int svgd_ksd_kernel(svgd_ctx *ctx, int kernel, const double *G_shard, double a, 
  * (SVGD_ERR_ARG); dim < 1 or n < 1 (SVGD_ERR_DIM). */
 int svgd_ksd_host(int kernel, int dim, int64_t n, const double *X, const double *G, double a,
                   double *ksd2_v, double *ksd2_u, double *rows_out);
+/* Maximum mean discrepancy (Gretton et al. 2012) between the particles X
+ * (N x dim, all ranks) and the caller's sample Y (m x dim, row-major like the
+ * particle rows), with the kernel named in the call and the scale a > 0:
+ *   SVGD_KERNEL_RBF  k = exp(-a |x - y|^2)
+ *   SVGD_KERNEL_IMQ  k = (1 + a |x - y|^2)^(-1/2)
+ *   Sxx = sum_{i,j<N} k(x_i, x_j),  Syy = sum_{i,j<m} k(y_i, y_j)   (the diagonal counts 1 each)
+ *   Sxy = sum_{i<N} sum_{j<m} k(x_i, y_j)
+ *   mean_xx = Sxx / N^2,  mean_yy = Syy / m^2,  mean_xy = Sxy / (N m)
+ *   MMD2_V  = mean_xx + mean_yy - 2 mean_xy                      (biased, >= 0 up to rounding)
+ *   MMD2_U  = (Sxx - N) / (N (N - 1)) + (Syy - m) / (m (m - 1)) - 2 mean_xy   (NaN if N < 2 or m < 2)
+ *   wit_i   = (1/N) sum_j k(x_i, x_j) - (1/m) sum_j k(x_i, y_j)
+ * means3_out = [mean_xx, mean_yy, mean_xy]; witness_shard_out (this rank's
+ * rows, shard layout like svgd_get_shard) takes wit_i, the witness function
+ * at particle i: positive where the particles are over-dense relative to Y.
+ * Any output may be NULL.  The contract is svgd_ksd_kernel's: fp64 whatever
+ * the dtype, blind to svgd_set_kernel, equal bits on equal state, a pure
+ * observer with work arrays of its own (allocated by the first call, grown
+ * when a later m needs it).  Collective in multi-GPU mode: every rank passes
+ * the same Y and gets the same scalars and means.  SVGD_ERR_ARG: NULL Y, an
+ * unknown kernel, a not finite or <= 0, a non-finite value in Y;
+ * SVGD_ERR_DIM: m < 1.  d <= 64. */
+int svgd_mmd(svgd_ctx *ctx, int kernel, const double *Y, int64_t m, double a, double *mmd2_v, double *mmd2_u,
+             double *means3_out, double *witness_shard_out);
+/* host, no GPU: the same quantities of X (n x dim) and Y (m x dim) by direct
+ * differences (no centring, no Gram form); witness_out (n, may be NULL) takes
+ * wit_i.  OpenMP over rows, each row's sum in column order and the sums over
+ * rows in row order (independent of the thread count).  Refused: NULL X or Y,
+ * an unknown kernel, a not finite or <= 0, a non-finite value in Y
+ * (SVGD_ERR_ARG); dim < 1, n < 1 or m < 1 (SVGD_ERR_DIM). */
+int svgd_mmd_host(int kernel, int dim, int64_t n, const double *X, int64_t m, const double *Y, double a,
+                  double *mmd2_v, double *mmd2_u, double *means3_out, double *witness_out);
 /* Stein thinning (Riabiz et al. 2022): the greedy choice of m of the current
  * particles whose empirical measure has the smallest KSD under the kernel
  * named in the call, with u_ij and u_ii as above for svgd_ksd /

@@ -93,6 +93,9 @@ SIGNATURES = {
     "svgd_ksd": (ctypes.c_int, [_P, _D, ctypes.c_double, _D, _D, _D]),
     "svgd_ksd_kernel": (ctypes.c_int, [_P, ctypes.c_int, _D, ctypes.c_double, _D, _D, _D]),
     "svgd_ksd_host": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _I64, _D, _D, ctypes.c_double, _D, _D, _D]),
+    "svgd_mmd": (ctypes.c_int, [_P, ctypes.c_int, _D, _I64, ctypes.c_double, _D, _D, _D, _D]),
+    "svgd_mmd_host": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _I64, _D, _I64, _D, ctypes.c_double, _D, _D, _D,
+                                     _D]),
     "svgd_stein_thin": (ctypes.c_int, [_P, ctypes.c_int, _D, ctypes.c_double, _I64, ctypes.POINTER(_I64), _D]),
     "svgd_stein_thin_host": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _I64, _D, _D, ctypes.c_double, _I64,
                                             ctypes.POINTER(_I64), _D]),

@@ -1116,6 +1116,29 @@ class Context:
                                                 ctypes.byref(u), C.dptr(out)))
         return (v.value, u.value, out) if rows else (v.value, u.value)
 
+    def mmd(self, Y, a=None, kernel="rbf", witness=False, means=False):
+        """Maximum mean discrepancy between the current particles and the
+        sample Y (m, d) (svgd_mmd; collective, every rank passes the same Y),
+        with the kernel named here whatever kernel the context steps with:
+        (MMD²_V, MMD²_U), then this rank's witness rows wit_i = (1/N) Σ_j
+        k(x_i, x_j) − (1/m) Σ_j k(x_i, y_j) when witness=True, then
+        [mean_xx, mean_yy, mean_xy] when means=True.  a: the kernel scale
+        (None: median_scale() of the particles)."""
+        kind = self.KERNELS.get(kernel, kernel) if isinstance(kernel, str) else kernel
+        if kind not in (C.SVGD_KERNEL_RBF, C.SVGD_KERNEL_IMQ):
+            raise ValueError(PREFIX + "[Argument Error] Invalid kernel kind.")
+        Y = np.ascontiguousarray(Y, dtype=np.float64)
+        if Y.ndim != 2 or Y.shape[1] != self.dim:
+            raise DimensionMismatchException("MMD sample has incorrect dimensions.")
+        if a is None:
+            a = self.median_scale()[0]
+        v, u = ctypes.c_double(), ctypes.c_double()
+        wit = np.empty(self.row1 - self.row0) if witness else None
+        m3 = np.empty(3) if means else None
+        self.check(self.lib.svgd_mmd(self.h, int(kind), C.dptr(Y), Y.shape[0], float(a), ctypes.byref(v),
+                                     ctypes.byref(u), C.dptr(m3), C.dptr(wit)))
+        return (v.value, u.value) + ((wit,) if witness else ()) + ((m3,) if means else ())
+
     def stein_thin(self, m, G_shard=None, a=None, kernel="imq", trace=False):
         """Stein thinning of the current particles (svgd_stein_thin;
         collective): the global row indices of the m greedily chosen points
@@ -1362,6 +1385,36 @@ class SVGD:
         try:
             c.set_particles(P)
             v, u = c.ksd(G[c.row0:c.row1], a, kernel=kind)
+        finally:
+            if c is not self.ctx:
+                c.close()
+        return u if unbiased else v
+
+    def ComputeMMD(self, Y, unbiased=False, kernel=None):
+        """MMD² between the caller's coordinate matrix and the sample Y (d, M),
+        columns are points like the coordinate matrix (extension; svgd_mmd on
+        the device): the biased V-statistic, or the U-statistic when unbiased.
+        The kernel, the scale and the context are handled as in ComputeKSD."""
+        kind = "rbf" if kernel is None else kernel
+        if kind not in Context.KERNELS:
+            raise ValueError(PREFIX + "[Argument Error] Invalid kernel kind.")
+        P = np.ascontiguousarray(np.asarray(self.coord_matrix_, dtype=np.float64).T)
+        Y = np.asarray(Y, dtype=np.float64)
+        if Y.ndim != 2 or Y.shape[0] != P.shape[1]:
+            raise DimensionMismatchException("MMD sample has incorrect dimensions.")
+        k = self.kernel_
+        a = None
+        if kind == "rbf":
+            if (isinstance(k, GaussianRBFKernel) and k.scale_matrix_ is None
+                    and k.scale_method_ == GaussianRBFKernel.ScaleMethod.Constant):
+                a = k.scale_
+        elif (isinstance(k, InverseMultiquadricKernel)
+                and k.scale_method_ == InverseMultiquadricKernel.ScaleMethod.Constant):
+            a = k.scale_
+        c = self.ctx if self.ctx is not None else Context(P.shape[1], P.shape[0], device=self.device_)
+        try:
+            c.set_particles(P)
+            v, u = c.mmd(np.ascontiguousarray(Y.T), a, kernel=kind)
         finally:
             if c is not self.ctx:
                 c.close()

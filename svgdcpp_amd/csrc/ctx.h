@@ -3,7 +3,7 @@
 // One context = one GPU (one process per GPU in multi-GPU runs).  The context
 // owns every resource it allocates (resource.h): deleting it frees them all.
 // State that one unit alone reads or writes sits in that unit's group (co,
-// sym, ms, hs, tm, dm, ksd, ksdq, thin, pred, imq); what several units share stays flat.  The units
+// sym, ms, hs, tm, dm, ksd, ksdq, mmd, thin, pred, imq); what several units share stays flat.  The units
 // (ctx_*.cpp, svgd_capi.cpp) call each other through the functions declared
 // at the end, per unit.
 #pragma once
@@ -405,6 +405,24 @@ struct svgd_ctx {
         svgd_amd::DevBuf<double> rec, diag;          // ksd_imq_padded(n) records, |s|^2 + ad
         svgd_amd::DevBuf<double> part, rows, bpart, out;
     } ksdq;
+
+    // svgd_mmd's own work arrays (allocated by its first call, the sample's
+    // side grown when a later call brings more points): it reads X and
+    // nothing else of the step's state
+    struct Mmd {
+        bool ready = false;
+        int cus = 0;                        // the device's CUs
+        int bpc[2] = {1, 1};                // work-groups of the pass one CU holds, per kernel (mmd_blocks_per_cu)
+        int64_t m_cap = 0;                  // sample points the Y side holds
+        int64_t ldp = 0;                    // partial stride: rows of X's shard or of Y's, whichever is more
+        int64_t part_cap = 0;               // doubles of part
+        svgd_amd::DevBuf<double> mu, mpart; // the particles' mean, its column-sum partials
+        svgd_amd::DevBuf<double> xrec;      // mmd_padded(n) records of mmd_rec_stride(d) doubles
+        svgd_amd::DevBuf<double> Y, yrec;   // the sample (m_cap x d) and its mmd_padded(m_cap) records
+        svgd_amd::DevBuf<double> part;      // S x ldp partial row sums (one pass at a time)
+        svgd_amd::DevBuf<double> rxx, rxy, ryy; // ldp row sums of each pass
+        svgd_amd::DevBuf<double> bpart, out;    // the finish's block partials; [Sxx, Sxy, Syy, -]
+    } mmd;
 
     // svgd_stein_thin's own work arrays (allocated by its first call, idx and S
     // grown when a call asks for more picks): the selection reads X and
